@@ -17,10 +17,20 @@ also subtracts the loss term) and ONE RCCL all-reduce (torch.distributed "nccl")
 
 What `value` times, for every N: K evaluations issued in order on one stream, evaluation i+1 starting after
 evaluation i -- including its collective -- has finished on the device (what a time stepper that needs Q_i to form
-f_{i+1} sees; no host round trip between evaluations).  Reported beside it, never as `value`:
+f_{i+1} sees; no host round trip between evaluations).  A plain run does only that: set-up, W warm-up evaluations,
+the K timed ones, the JSON line.  With --full it also measures, beside `value` and never as `value`:
+  repeats       : further K-step loops of the same kind (median / min / max);
   blocking_call : every evaluation followed by a host synchronisation, the reference driver's timing loop
                   (maxwell_bkw_cuda.cu:144-151; bfsm_collide at N = 1);
-  overlapped    : N > 1 only -- the all-reduce of evaluation i left in flight under the gain kernels of i+1.
+  overlapped    : N > 1 only -- the all-reduce of evaluation i left in flight under the gain kernels of i+1;
+  roofline      : per-kernel HIP-event times of a profiled handle, the dominant kernel against HBM peak;
+  exact_reductions : the opt-in exact work reductions, timed like `value`;
+  cpu_baseline  : N = 1 only -- the CPU oracle on this host's cores.
+--repeats 0, --no-extras, --no-roofline, --no-exact and --no-cpu-baseline drop single items of --full; without --full
+these objects are null.
+
+--dump-outputs DIR: after the timed loop, rank 0 writes Q of the last timed evaluation (what a caller of the timed
+path receives; the input f is the same on every run with the same arguments) to DIR/Q.npy, float64.
 
 Workloads (BASELINE.json configs):  cfg2 N=32,M_gl=8,ss009.048 | cfg3 N=64,M_gl=16,ss009.048 (default, the
 roofline configuration) | cfg4 N=64,M_gl=16,ss017.156 | cfg5 N=128,M_gl=30,ss019.192 fp32.
@@ -124,6 +134,14 @@ def kernel_source_digest():
     return h.hexdigest()[:16]
 
 
+def dump_outputs(d, q):
+    """--dump-outputs: the collision term of the last timed evaluation as DIR/Q.npy (float64; 2 MiB at cfg3, 16 MiB at
+    cfg5), for output-by-output comparisons of two builds on the same input."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "Q.npy"), np.ascontiguousarray(q, dtype=np.float64))
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -154,12 +172,18 @@ def main():
     ap.add_argument("--max-chunk", type=int, default=0)
     ap.add_argument("--precision", type=int, default=0, choices=(0, 32, 64),
                     help="override the workload's arithmetic type (0 = the workload's own)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-exact", action="store_true", help="skip the extra opt-in exact-reduction measurement")
-    ap.add_argument("--no-extras", action="store_true", help="skip the blocking_call / overlapped side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (repeats, blocking_call / overlapped, roofline, exact_reductions, "
+                         "cpu_baseline); a plain run times the headline loop only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write Q of the last timed evaluation to DIR/Q.npy (float64, rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline object")
+    ap.add_argument("--no-exact", action="store_true", help="with --full: skip the opt-in exact-reduction measurement")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the blocking_call / overlapped measurements")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="extra K-step loops after the headline loop; their median / min / max go to the `repeats` key")
+                    help="with --full: extra K-step loops after the headline loop; their median / min / max go to the "
+                         "`repeats` key")
     ap.add_argument("--rehearsal", action="store_true",
                     help="CPU plumbing rehearsal of the N>1 launch path (no GPU, no measurement): the ranks are started, "
                          "form a gloo group, shard the directions and run the collective with the tests' host emulator "
@@ -168,6 +192,9 @@ def main():
 
     if args.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         sys.exit(2)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -325,13 +352,15 @@ def main():
             dist.all_reduce(Q2, async_op=True).wait()
         fence()
     elapsed = timed(op, "inorder")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, Q.cpu().numpy())     # Q of the last timed evaluation (fenced by timed())
 
     ms_per_step = 1e3 * elapsed / args.steps
     evals_per_s = args.steps / elapsed
     # `value` is the driver's K steps above.  One K-step sample of a few tens of ms moves with the chip's clock / power
     # state; the spread of further identical K-step loops is reported beside it (never as `value`).
     repeats = None
-    if args.repeats > 0:
+    if args.full and args.repeats > 0:
         import statistics
         rates = sorted(args.steps / timed(op, "inorder") for _ in range(args.repeats))
         repeats = {"n": args.repeats, "steps_each": args.steps, "median": statistics.median(rates), "min": rates[0],
@@ -342,7 +371,7 @@ def main():
     alg_gbps = alg_bytes / (elapsed / args.steps) / 1e9
 
     blocking = overlapped = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         el = timed(op, "blocking")
         blocking = {"value": args.steps / el, "unit": "evals/s", "ms_per_step": 1e3 * el / args.steps,
                     "note": "host synchronisation after every evaluation (maxwell_bkw_cuda.cu:144-151)"}
@@ -352,7 +381,7 @@ def main():
                           "note": "all-reduce of evaluation i in flight under the gain kernels of evaluation i+1"}
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # dominant kernel, timed live with HIP events on the stream it is launched on (BFSM_FLAG_PROFILE)
         opp = make(True)
         s = torch.cuda.current_stream().cuda_stream
@@ -418,7 +447,7 @@ def main():
     # transforms, product and x part of the forward transform, every array written and read once per direction (6 array
     # passes); only the (y,z) part of the forward transform acts on a segment's weighted sum (config.kc_sum_before_transform).
     exact = None
-    if not args.no_exact:
+    if args.full and not args.no_exact:
         ope = make(False, exact=True)
         el = timed(ope, "inorder")
         cn = ope.counters()
@@ -432,7 +461,7 @@ def main():
         ope.destroy()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(w)
 
     op.destroy()
@@ -446,7 +475,7 @@ def main():
             "metric": "collision-operator evals/sec", "value": evals_per_s, "unit": "evals/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f64" if prec == 64 else "f32", "data": "synthetic",
+            "dtype": "f64" if prec == 64 else "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{args.workload}: N={nv}^3 grid, M_gl={n_gl}, {w['design']} ({n_sph} pts), "
                                    f"B={B} directions, BKW f (t=6.5), Maxwell molecules",
                        "directions_per_gpu": B // world,
@@ -500,6 +529,8 @@ def rehearsal(args, world, rank):
     Qw = torch.empty_like(f)
     bfsm.sharded_step(whole, whole.qhat, Qw, f, None)
     err = float((Q - Qw).abs().max() / Qw.abs().max())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, Q.numpy().reshape(nv, nv, nv))
     if rank == 0:
         print(json.dumps({"metric": "collision-operator evals/sec", "value": None, "unit": "evals/s", "n_gpus": world,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": None, "higher_is_better": True,

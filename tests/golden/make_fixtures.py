@@ -8,6 +8,10 @@ results shows up as a diff against committed data, and so that the GPU tests als
 
   q_cfg1_bkw.npy     Q for BASELINE config 1 (N=16, M_gl=8, 32-point design), BKW f at t = 6.5
   q_cfg1_random.npy  same operator, seeded perturbed f (oracle.perturbed_input, seed 0x5EED, amp 0.1)
+
+  ref_sph_designs.npz  the reference's own spherical-design tables (Quadratures/ssTTT.NNN.txt), parsed to doubles, one
+                       (NNN, 3) array per file keyed "ssTTT.NNN"; data only, written by
+                       `make_fixtures.py --designs <reference checkout>/Quadratures`
 """
 import os
 import sys
@@ -19,7 +23,18 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle"
 import oracle as O  # noqa: E402
 
 
+def designs(qdir):
+    import glob
+    tables = {}
+    for p in sorted(glob.glob(os.path.join(qdir, "ss*.txt"))):
+        tables[os.path.basename(p)[:-4]] = np.array([[float(v) for v in ln.split()] for ln in open(p) if ln.strip()])
+    np.savez(os.path.join(HERE, "ref_sph_designs.npz"), **tables)
+    print("written ref_sph_designs.npz", sorted(tables))
+
+
 def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--designs":
+        return designs(sys.argv[2])
     f, _, L, _ = O.bkw(16)
     gl = O.gauss_legendre(8, 0.0, 10.0)
     sph = O.spherical_design(32)

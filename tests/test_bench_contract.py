@@ -1,5 +1,6 @@
 """bench.py's contract with the driver: without a GPU it fails loudly (no CPU path), on a GPU it prints ONE JSON line
-carrying every required key, the roofline object and the CPU baseline."""
+carrying every required key; with --full also the roofline object and the CPU baseline; --dump-outputs writes the Q of
+the last timed evaluation."""
 import json
 import os
 import subprocess
@@ -44,9 +45,39 @@ def test_bench_gpus_2_launches_its_own_ranks_cpu_rehearsal():
     assert d["sharded_vs_whole_rel_err"] <= 1e-13
 
 
+def test_bench_options_are_listed():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+def test_bench_rejects_zero_steps():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         timeout=120)
+    assert out.returncode == 2 and "--steps" in out.stderr
+
+
+def test_bench_rehearsal_dumps_the_collision_term(oracle, tmp_path):
+    """--dump-outputs on the CPU rehearsal (one rank, the host emulator of the kernels on the rehearsal's N = 16 grid):
+    DIR/Q.npy is the collision term of the BKW input, the oracle's to 1e-12."""
+    import numpy as np
+    import bfsm
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--rehearsal",
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600, env=env,
+                         cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    got = np.load(tmp_path / "out" / "Q.npy")
+    assert got.dtype == np.float64 and got.shape == (16, 16, 16)
+    c = bfsm.reference_constants()
+    ref = oracle.collide(bfsm.bkw_solution(16)[0], oracle.gauss_legendre(2, 0.0, c["R"]), oracle.spherical_design(12),
+                         c["gamma"], c["b_gamma"], c["L"])
+    assert np.abs(got - ref).max() <= 1e-12 * np.abs(ref).max()
+
+
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -80,3 +111,31 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert r["per_kernel_sum_ms"] <= 1.03 * d["ms_per_step"], (r["per_kernel_sum_ms"], d["ms_per_step"])
     rp = d["repeats"]
     assert rp["n"] == 5 and rp["min"] <= rp["median"] <= rp["max"] and 0.8 * d["value"] < rp["median"] < 1.25 * d["value"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_only_and_dumps_q(tmp_path):
+    """A plain run (no --full) times the headline loop and nothing else: the side objects are null.  --dump-outputs
+    writes the Q of the last timed cfg3 evaluation, which reproduces the reference's BKW norms at cfg3."""
+    import numpy as np
+    import bfsm
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["full"] is False and d["dtype"] == "f64"
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] - 1000.0) < 1e-6 * 1000.0
+    for k in ("roofline", "cpu_baseline", "blocking_call", "overlapped", "exact_reductions", "repeats"):
+        assert d[k] is None, k
+    got = np.load(tmp_path / "out" / "Q.npy")
+    assert got.dtype == np.float64 and got.shape == (64, 64, 64)
+    row = [r for r in json.load(open(os.path.join(ROOT, "tests", "golden", "bkw_norms.json")))["survey"]
+           if r["nv"] == 64][0]
+    _, q_exact, _, dv = bfsm.bkw_solution(64)
+    l1, l2, linf = bfsm.error_norms(got, q_exact, dv)
+    assert abs(l2 - row["L2"]) <= 1e-10
+    for name, val in (("L1", l1), ("L2", l2), ("Linf", linf)):
+        assert val == pytest.approx(row[name], rel=6e-9), name
+    assert np.abs(got).sum() == pytest.approx(row["sum_abs_Q"], rel=2e-10)

@@ -638,7 +638,7 @@ def test_bench_two_ranks_rehearsal(torch_cuda):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(BFSM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "cfg2", "--no-roofline"],
+                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "cfg2", "--full", "--no-roofline"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -1,9 +1,24 @@
 """Builds (g++, no GPU, no HIP) and runs the C++ checks of the host-side mirror of the reference interface."""
 import os
+import platform
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "boltzmann-fourier-spectral-method_amd")
+
+
+def _tsan_launcher():
+    """Prefix for running a ThreadSanitizer binary.  GCC 11's TSan runtime expects the address-space layout of 28 bits of
+    mmap randomisation; on a kernel that randomises more (vm.mmap_rnd_bits = 32) the executable or a library can land
+    outside its application ranges, and the binary dies at start-up ("FATAL: ThreadSanitizer: unexpected memory
+    mapping", or SIGSEGV).  Newer TSan runtimes then re-execute themselves with randomisation off; this does the same
+    from outside (setarch -R: for that one process), wherever the personality switch is permitted."""
+    cmd = ["setarch", platform.machine(), "-R"]
+    try:
+        ok = subprocess.run(cmd + ["true"], capture_output=True, timeout=60).returncode == 0
+    except (OSError, subprocess.SubprocessError):
+        ok = False
+    return cmd if ok else []
 
 
 def test_cpp_host_mirror(tmp_path):
@@ -48,7 +63,9 @@ def test_multigpu_operator_choreography_with_p_gt_1(tmp_path, sanitizer):
                            os.path.join(ROOT, "tests", "host", "test_multigpu_choreography.cpp"),
                            os.path.join(PKG, "host", "Quadratures", "SphericalDesign.cpp"), "-o", exe])
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1 exitcode=66")
-    out = subprocess.run([exe, os.path.join(PKG, "data", "sph_design")], capture_output=True, text=True, timeout=600, env=env)
+    launcher = _tsan_launcher() if sanitizer == "thread" else []
+    out = subprocess.run(launcher + [exe, os.path.join(PKG, "data", "sph_design")], capture_output=True, text=True,
+                         timeout=600, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert "multi-GPU choreography checks passed" in out.stdout and "ThreadSanitizer" not in out.stderr
 

@@ -141,15 +141,18 @@ def test_spherical_designs(oracle):
         oracle.spherical_design(13)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Quadratures"), reason="reference tree not mounted")
 def test_design_tables_bit_identical_to_reference_data(oracle):
-    """Our re-encoded data tables hold exactly the doubles of the reference's ssTTT.NNN.txt files."""
-    import glob
+    """Our re-encoded data tables hold exactly the doubles of the reference's ssTTT.NNN.txt files (kept as the data
+    fixture tests/golden/ref_sph_designs.npz, see make_fixtures.py)."""
     import re
-    for p in glob.glob("/root/reference/Quadratures/ss*.txt"):
-        n = int(re.match(r"ss\d+\.(\d+)\.txt", os.path.basename(p)).group(1))
-        ref = np.array([[float(v) for v in ln.split()] for ln in open(p) if ln.strip()])
+    ref_tables = np.load(os.path.join(HERE, "golden", "ref_sph_designs.npz"))
+    assert sorted(int(re.fullmatch(r"ss\d+\.(\d+)", k).group(1)) for k in ref_tables.files) == \
+        [6, 12, 32, 48, 70, 94, 120, 156, 192]
+    for key in ref_tables.files:
+        n = int(key.split(".")[1])
+        ref = ref_tables[key]
         x, y, z, _ = oracle.spherical_design(n)
+        assert ref.shape == (n, 3)
         assert np.array_equal(ref, np.stack([x, y, z], axis=1))
 
 

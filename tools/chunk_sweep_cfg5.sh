@@ -3,7 +3,7 @@
 # with the interleaved layout + P'):  bash tools/chunk_sweep_cfg5.sh [sizes...]
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 for mc in ${@:-576 720 960 1152 1440 1920 2880}; do
-  python3 $R/bench.py --workload cfg5 --max-chunk $mc --steps 3 --warmup 1 --no-extras --no-exact --no-cpu-baseline --no-roofline --repeats 2 2>/dev/null |
+  python3 $R/bench.py --full --workload cfg5 --max-chunk $mc --steps 3 --warmup 1 --no-extras --no-exact --no-cpu-baseline --no-roofline --repeats 2 2>/dev/null |
     python3 -c "
 import json, sys
 d = json.loads(sys.stdin.readline())

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out
 cd $GRAFT_REPO_ROOT
 rm -rf $O/pmc_clk
-timeout -k 10 200 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_clk -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-exact > $O/pmc_clk.log 2>&1
+timeout -k 10 200 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_clk -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-exact > $O/pmc_clk.log 2>&1
 python3 - <<'PY'
 import csv, glob, collections, re, os
 O = os.environ.get("GRAFT_REPO_ROOT", ".") + "/gpurun_out"

@@ -17,11 +17,11 @@ O=$R/gpurun_out
 cd $R
 rm -rf $O/prof_stats $O/prof_fetch $O/prof_write
 STEPS=20; [ "$WL" = cfg5 ] && STEPS=5; [ "$WL" = cfg4 ] && STEPS=10
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 bench.py --workload $WL --steps $STEPS --warmup 3 --no-cpu-baseline --no-exact --no-extras $EXTRA > $O/prof_stats.log 2>&1
-timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/prof_fetch -- python3 bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-exact --no-roofline --no-extras $EXTRA > $O/prof_fetch.log 2>&1
-timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/prof_write -- python3 bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-exact --no-roofline --no-extras $EXTRA > $O/prof_write.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 bench.py --full --workload $WL --steps $STEPS --warmup 3 --no-cpu-baseline --no-exact --no-extras $EXTRA > $O/prof_stats.log 2>&1
+timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/prof_fetch -- python3 bench.py --full --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-exact --no-roofline --no-extras $EXTRA > $O/prof_fetch.log 2>&1
+timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/prof_write -- python3 bench.py --full --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-exact --no-roofline --no-extras $EXTRA > $O/prof_write.log 2>&1
 python3 profiles/summarize.py ${TAG}_$WL $O/prof_stats $O/prof_fetch $O/prof_write "tag $TAG: python3 bench.py --workload $WL $EXTRA" $WL
-timeout -k 10 600 python3 bench.py --workload $WL $EXTRA > $O/bench_${TAG}_$WL.json 2> $O/bench_${TAG}_$WL.err
+timeout -k 10 600 python3 bench.py --full --workload $WL $EXTRA > $O/bench_${TAG}_$WL.json 2> $O/bench_${TAG}_$WL.err
 mkdir -p $O/profiles_$TAG
 python3 tools/launch_gaps.py $O/prof_stats > $O/profiles_$TAG/${TAG}_${WL}_launch_gaps.txt 2>&1 || true
 cp profiles/${TAG}_${WL}_kernel_stats.csv profiles/${TAG}_${WL}_pmc_traffic.json $O/profiles_$TAG/
