@@ -17,7 +17,7 @@ EXPORTED_SYMBOLS = (
     "bfsm_create", "bfsm_collide", "bfsm_collide_async", "bfsm_collide_batch", "bfsm_collide_batch_async", "bfsm_collide_batch_partial_async", "bfsm_gain_partial", "bfsm_finish", "bfsm_finish_partial", "bfsm_collide_partial_async",
     "bfsm_qhat_buffer",
     "bfsm_synchronize", "bfsm_fft3d", "bfsm_get_counters", "bfsm_destroy", "bfsm_last_error", "bfsm_backend_name",
-    "bfsm_version",
+    "bfsm_version", "bfsm_collide_bilinear", "bfsm_collide_bilinear_async", "bfsm_collide_bilinear_partial_async",
 )
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -95,6 +95,12 @@ def load_library(path=None):
     L.bfsm_finish_partial.restype = ctypes.c_int
     L.bfsm_collide_partial_async.argtypes = [vp, vp, vp, ctypes.c_int, vp]
     L.bfsm_collide_partial_async.restype = ctypes.c_int
+    L.bfsm_collide_bilinear.argtypes = [vp, vp, vp, vp]
+    L.bfsm_collide_bilinear.restype = ctypes.c_int
+    L.bfsm_collide_bilinear_async.argtypes = [vp, vp, vp, vp, vp]
+    L.bfsm_collide_bilinear_async.restype = ctypes.c_int
+    L.bfsm_collide_bilinear_partial_async.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp]
+    L.bfsm_collide_bilinear_partial_async.restype = ctypes.c_int
     L.bfsm_qhat_buffer.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
     L.bfsm_qhat_buffer.restype = vp
     L.bfsm_synchronize.argtypes = [vp]

@@ -33,6 +33,7 @@ class HIPBoltzmannOperator:
         self._max_batch = 0
         self._h = None
         self._lib = None
+        self._lin_tmp = None
 
     # knobs, to be set before initialize() -- like setWisdomFileName in the FFTW backend (FFTWBoltzmannOperator.hpp:39-41)
     def setPrecision(self, bits):
@@ -136,6 +137,40 @@ class HIPBoltzmannOperator:
         self._check(self._lib.bfsm_collide_batch_partial_async(self._h, _ptr(Q), _ptr(f_in), int(n_batch),
                                                                1 if with_loss else 0, ctypes.c_void_p(stream)))
 
+    # Bilinear form Q(g,f) (include/bfsm.h): gain with A1 from g_hat and A2 from f_hat, loss g * Re IFFT(beta2 f_hat / G).
+    # Q(f,f) is computeCollision; handles with exact reductions raise (BFSM_ERR_UNSUPPORTED).
+    def computeBilinearCollision(self, Q, g, f):
+        """Blocking Q = Q(g, f), device tensors."""
+        self._require(g, Q)
+        self._require(f)
+        self._check(self._lib.bfsm_collide_bilinear(self._h, _ptr(Q), _ptr(g), _ptr(f)))
+
+    def computeBilinearCollisionAsync(self, Q, g, f, stream=0):
+        self._require(g, Q)
+        self._require(f)
+        self._check(self._lib.bfsm_collide_bilinear_async(self._h, _ptr(Q), _ptr(g), _ptr(f), ctypes.c_void_p(stream)))
+
+    def collideBilinearPartial(self, Q, g, f, with_loss, stream=0):
+        """This shard's part of Q(g, f) [- the loss term if with_loss]; the caller sums Q over the ranks."""
+        self._require(g, Q)
+        self._require(f)
+        self._check(self._lib.bfsm_collide_bilinear_partial_async(self._h, _ptr(Q), _ptr(g), _ptr(f), 1 if with_loss else 0,
+                                                                  ctypes.c_void_p(stream)))
+
+    def linearizedCollision(self, Q, f, h, tmp=None):
+        """Blocking Q = L_f[h] = Q(f, h) + Q(h, f), the Jacobian of Q at f applied to h (two bilinear evaluations).
+        tmp: optional caller-owned device tensor of the same shape; otherwise a handle-owned one is allocated once."""
+        self._require(f, Q)
+        self._require(h)
+        if tmp is None:
+            if self._lin_tmp is None or self._lin_tmp.device != Q.device:
+                self._lin_tmp = Q.new_empty(Q.shape)
+            tmp = self._lin_tmp
+        self._require(tmp)
+        self.computeBilinearCollision(Q, f, h)
+        self.computeBilinearCollision(tmp, h, f)
+        Q.add_(tmp.view(Q.shape))
+
     def gainPartial(self, f_in, stream=0):
         self._require(f_in)
         self._check(self._lib.bfsm_gain_partial(self._h, _ptr(f_in), ctypes.c_void_p(stream)))
@@ -178,6 +213,7 @@ class HIPBoltzmannOperator:
         if self._h is not None and self._lib is not None:
             self._lib.bfsm_destroy(self._h)
         self._h = None
+        self._lin_tmp = None
 
     def __del__(self):
         try:

@@ -521,6 +521,15 @@ struct GainInvParams {       // KA
     int warm_tables;         // != 0: touch the phase-table rows two iterations ahead (tables larger than an XCD's L2)
 };
 
+// KA of the bilinear form Q(g,f): the alpha tile (A1') is formed from fhat = g_hat, the conj(alpha) tile (A2') from
+// fhat2 = f_hat.  A parameter type of its own, so that the Q(f,f) instantiations are the code they were.
+template <typename T>
+struct GainInvBiParams : GainInvParams<T> {
+    const cx<T>* fhat2;      // [lx][lz][ly], same layout as fhat
+};
+template <class P> struct ka_bilinear { static constexpr bool value = false; };
+template <typename T> struct ka_bilinear<GainInvBiParams<T>> { static constexpr bool value = true; };
+
 // Hermitian mode where KN's workgroups have KA's shape (nyq_rides_along): the Nyquist-row transforms of the chunk run
 // as extra workgroups of KA's launch -- blockIdx.y >= ka_groups -- instead of as a launch of their own
 template <typename T>
@@ -803,9 +812,13 @@ template <int N, typename T> constexpr size_t ka_xlane_lds_bytes() { return ((si
 // fused with the (lz,ly) -> (y,z) part of the two batched inverse transforms (CUDABoltzmannOperator.cu:156-164).
 // PAIRS: store {A1', A2'} pairs into a1 (ab_interleaved geometries); false there only for the Hermitian mode's launches
 // (kernel kind GainInvTwo), which keep two arrays.
-template <int N, typename T, bool PAIRS = ab_interleaved<N, T>(), class Ctx>
-BFSM_HD void body_gain_inv(const GainInvParams<T>& prm, Ctx& ctx) {
+// Bilinear form (P = GainInvBiParams): the alpha tile from fhat (g_hat, the plane kept in registers where KEEP), the
+// conj(alpha) tile from fhat2 (f_hat), re-read per direction from L2 like the REREAD geometries: a second resident plane
+// would not fit next to the kernels at their register caps (N = 64 fp64, N = 128 fp32).
+template <int N, typename T, bool PAIRS = ab_interleaved<N, T>(), class Ctx, class P>
+BFSM_HD void body_gain_inv(const P& prm, Ctx& ctx) {
     static_assert(!PAIRS || ab_interleaved<N, T>(), "pair stores need the pipelined-pair form");
+    constexpr bool BILIN = ka_bilinear<P>::value;
     constexpr int E = Wg<N>::E, TT = Wg<N>::T;
     int p, u;
     lane_coords<N, Wg<N>::ROW>(ctx, p, u);
@@ -817,13 +830,19 @@ BFSM_HD void body_gain_inv(const GainInvParams<T>& prm, Ctx& ctx) {
     // The workgroup's f_hat plane stays in registers across the direction loop, except in the one geometry whose
     // 1024-thread workgroup leaves 128 VGPRs for 2 x 64 of data (N = 128, fp64): there it is re-read every
     // iteration (a 256 KiB plane shared by the workgroups of the plane: L2 / Infinity Cache traffic).
-    constexpr bool KEEP = keep_plane<N, T>();
+    // Bilinear form at N = 80 in single precision: the g_hat plane is re-read as well (held next to the f_hat re-reads it
+    // pushes the kernel past its register cap: 60 bytes of scratch per lane)
+    constexpr bool KEEP = keep_plane<N, T>() && !(BILIN && sizeof(T) == 4 && N == 80);
     // re-read geometries: f_hat points in flight per batch (the split-exchange geometry has 4 registers' worth of room;
     // E = 24 has the transform's own registers free at that moment and few waves to hide the L2 latency behind)
     constexpr int REREAD = split_tile<N, T>() ? 4 : 12;
+    // bilinear form: f_hat points of the conj(alpha) tile in flight per batch (its plane is re-read next to the kept g_hat plane)
+    constexpr int REREAD_BI = 4;
     cx<T> fh[KEEP ? E : 1];
     const size_t bz = (size_t)ctx.bz();
     const cx<T>* src = prm.fhat + bz * N * N * N + (size_t)lxi * N * N;
+    const cx<T>* src2 = src;                     // the conj(alpha) tile's plane
+    if constexpr (BILIN) src2 = prm.fhat2 + bz * N * N * N + (size_t)lxi * N * N;
     if constexpr (KEEP) {
 #pragma unroll
         for (int m = 0; m < E; ++m) fh[m] = src[(u + TT * m) * N + p];  // [lz = u + T m][ly = p]
@@ -840,7 +859,7 @@ BFSM_HD void body_gain_inv(const GainInvParams<T>& prm, Ctx& ctx) {
         //    wr A, dft(B) | rd A | wr B, step2(A), store A | rd B | step2(B), store B
         // ("|" = barrier; 12 per direction instead of 14).  The phase factors are formed once per point and used for both
         // signs (the two tiles are live together here anyway).  Measured against the sequential form: see DESIGN.md 7.1.
-        constexpr bool XL = PAIRS && ka_xlane<N, T>();
+        constexpr bool XL = PAIRS && ka_xlane<N, T>() && !BILIN;     // (the cross-lane A/B form has no bilinear variant)
         constexpr int Q = Wg<N>::Q, LS = XL ? N + 4 : Wg<N>::LS;
         unsigned pl = (unsigned)p * (unsigned)sizeof(cx<T>);   // this lane's byte offset inside a row
         // Exchange addresses.  A tile beyond 64 KiB (N = 128) does not fit the 16-bit immediate offset of the LDS
@@ -1047,7 +1066,9 @@ BFSM_HD void body_gain_inv(const GainInvParams<T>& prm, Ctx& ctx) {
 #ifdef BFSM_KA_SHARE_PHASE
             constexpr bool SHARE = (BFSM_KA_SHARE_PHASE) != 0;
 #else
-            constexpr bool SHARE = sizeof(T) == 4 && N == 128;
+            // (not in the bilinear form: the two tiles read different planes, and the conj(alpha) tile's re-reads next to both
+            // tiles left 96 bytes of scratch per lane at N = 128 fp32)
+            constexpr bool SHARE = sizeof(T) == 4 && N == 128 && !BILIN;
 #endif
 #pragma unroll
             for (int m = 0; m < E; ++m) {
@@ -1055,7 +1076,9 @@ BFSM_HD void body_gain_inv(const GainInvParams<T>& prm, Ctx& ctx) {
                 cx<T> fm;
                 if constexpr (KEEP) fm = fh[m]; else fm = src[(u + TT * m) * N + p];   // plane not held: re-read (L2)
                 va[m] = cmul(fm, ph);           // alpha1 f_hat / G
-                if constexpr (SHARE) vb[m] = cmulc(fm, ph);          // conj(alpha1) f_hat / G
+                if constexpr (SHARE && BILIN) vb[m] = cmulc(ctx.template ld_at<ROWU>(src2 + (size_t)(u + TT * m) * N, pl), ph);
+                else if constexpr (SHARE) vb[m] = cmulc(fm, ph);     // conj(alpha1) f_hat / G
+                if constexpr (BILIN) { if ((m % REREAD_BI) == REREAD_BI - 1) ctx.sched_fence(); }
             }
             SmallDft<E, +1, T>::run(va);
             BFSM_TSYNC(0);                         // the previous direction's last exchange has been read
@@ -1066,8 +1089,11 @@ BFSM_HD void body_gain_inv(const GainInvParams<T>& prm, Ctx& ctx) {
 #pragma unroll
                 for (int m = 0; m < E; ++m) {
                     cx<T> fm;
-                    if constexpr (KEEP) fm = fh[m]; else fm = src[(u + TT * m) * N + p];
+                    // (re-read: wave-uniform row + the per-iteration lane offset, no address registers held across the loop)
+                    if constexpr (BILIN) fm = ctx.template ld_at<ROWU>(src2 + (size_t)(u + TT * m) * N, pl);
+                    else if constexpr (KEEP) fm = fh[m]; else fm = src[(u + TT * m) * N + p];
                     vb[m] = cmulc(fm, cmul(c0s, ctx.ldc(prm.phz + b * N + u + TT * m)));
+                    if constexpr (BILIN) { if ((m % REREAD_BI) == REREAD_BI - 1) ctx.sched_fence(); }
                 }
             }
             SmallDft<E, +1, T>::run(vb);
@@ -1145,9 +1171,11 @@ BFSM_HD void body_gain_inv(const GainInvParams<T>& prm, Ctx& ctx) {
                 for (int m = 0; m < E; ++m) {
                     const cx<T> ph = cmul(c0s, ctx.ldc(prm.phz + b * N + u + TT * m));
                     cx<T> fm;
-                    if constexpr (KEEP) fm = fh[m]; else fm = src[(u + TT * m) * N + p];
+                    if constexpr (BILIN && CONJ) fm = src2[(u + TT * m) * N + p];
+                    else if constexpr (KEEP) fm = fh[m]; else fm = src[(u + TT * m) * N + p];
                     v[m] = CONJ ? cmulc(fm, ph) : cmul(fm, ph);   // conj(alpha1) f_hat / G  :  alpha1 f_hat / G
                     if constexpr (!KEEP) { if ((m % REREAD) == REREAD - 1) ctx.sched_fence(); }   // at most REREAD re-read points in flight
+                    else if constexpr (BILIN && CONJ) { if ((m % REREAD_BI) == REREAD_BI - 1) ctx.sched_fence(); }
                 }
                 fft_tile<N, +1, T, true>(v, lds, p, u, twr, ctx);
                 cx<T>* dst = (CONJ ? prm.a2 : prm.a1) + bz * prm.a_bstride + ((size_t)d * prm.planes + lxi) * N * N;
@@ -1182,7 +1210,8 @@ BFSM_HD void body_gain_inv(const GainInvParams<T>& prm, Ctx& ctx) {
             for (int m = 0; m < E; ++m) {
                 const cx<T> ph = cmul(c0, ctx.ldc(prm.phz + b * N + u + TT * m));
                 cx<T> fm;
-                if constexpr (KEEP) fm = fh[m]; else fm = src[(u + TT * m) * N + p];
+                if constexpr (BILIN) { if (conj) fm = src2[(u + TT * m) * N + p]; else if constexpr (KEEP) fm = fh[m]; else fm = src[(u + TT * m) * N + p]; }
+                else if constexpr (KEEP) fm = fh[m]; else fm = src[(u + TT * m) * N + p];
                 v[m] = conj ? cmulc(fm, ph) : cmul(fm, ph);   // conj(alpha1) f_hat / G  :  alpha1 f_hat / G
                 if constexpr (!KEEP) { if ((m % REREAD) == REREAD - 1) ctx.sched_fence(); }   // at most REREAD re-read points in flight
             }
@@ -1229,9 +1258,10 @@ template <int N> constexpr bool pair_tile() {
 template <int N> constexpr int pair_threads() { return 2 * N * Wg<N>::T; }
 template <int N, typename T> constexpr size_t pair_lds_bytes() { return (size_t)N * (2 * N + 1) * sizeof(cx<T>); }
 
-template <int N, typename T, class Ctx>
-BFSM_HD void body_gain_inv_pair(const GainInvParams<T>& prm, Ctx& ctx) {
+template <int N, typename T, class Ctx, class P>
+BFSM_HD void body_gain_inv_pair(const P& prm, Ctx& ctx) {
     constexpr int E = Wg<N>::E, TT = Wg<N>::T, NP = 2 * N, LS = NP + 1;
+    constexpr bool BILIN = ka_bilinear<P>::value;
     const int tid = ctx.tid(), lane = tid % NP, u = ctx.uniform(tid / NP, NP);
     const int h = lane / N, p = lane % N;                  // h: 0 = alpha tile (A1'), 1 = conj(alpha) tile (A2')
     const T sg = h ? (T)-1 : (T)1;
@@ -1240,7 +1270,10 @@ BFSM_HD void body_gain_inv_pair(const GainInvParams<T>& prm, Ctx& ctx) {
     Twiddles<N, T> twr;
     twr.load(prm.tw, u, ctx);
     const size_t bz = (size_t)ctx.bz();
-    const cx<T>* src = prm.fhat + bz * N * N * N + (size_t)lxi * N * N;
+    // bilinear form: the conj(alpha) half holds the plane of the second spectrum (one plane per lane either way)
+    const cx<T>* fsrc = prm.fhat;
+    if constexpr (BILIN) { if (h) fsrc = prm.fhat2; }
+    const cx<T>* src = fsrc + bz * N * N * N + (size_t)lxi * N * N;
     cx<T> fh[E];
 #pragma unroll
     for (int m = 0; m < E; ++m) fh[m] = src[(u + TT * m) * N + p];  // [lz = u + T m][ly = p], both halves the same plane

@@ -40,7 +40,8 @@ enum : int { GEN_PLAIN = 0, GEN_PHASE = 1, GEN_PRODUCT = 2, GEN_REAL = 3, GEN_BE
 template <typename T>
 struct GenFftParams {
     const void* in;          // cx<T> arrays [batch][G]; GEN_REAL: const double* [batch][G]; GEN_PHASE / GEN_BETA2: f_hat [G]
-    const cx<T>* in2;        // GEN_PRODUCT: second factor, same shape as in
+    const cx<T>* in2;        // GEN_PRODUCT: second factor, same shape as in; GEN_PHASE of the bilinear form (GenFftBiParams):
+                             // the spectrum of the conj(alpha) members (s = 1), in holds that of the alpha members
     cx<T>* out;              // [batch][G]
     const cx<T>* tw;         // exp(-2 pi i k / n), k < n, n = length of the transformed axis
     int nx, ny, nz;
@@ -70,6 +71,13 @@ struct GenFftParams {
     int mper;
     size_t in_mstride, out_mstride;
 };
+
+// The bilinear form Q(g,f) launches the GEN_PHASE producers with this type: member s = 1 reads in2 (f_hat) instead of in
+// (g_hat).  A type of its own, so that the Q(f,f) instantiations are the code they were.
+template <typename T>
+struct GenFftBiParams : GenFftParams<T> {};
+template <class P> struct gen_bilinear { static constexpr bool value = false; };
+template <typename T> struct gen_bilinear<GenFftBiParams<T>> { static constexpr bool value = true; };
 
 template <typename T>
 struct GenAccParams {        // Q_hat[l] (+)= sum_d dirw[d] beta1[r(d)][|l|^2] P_hat[d][l], fixed order (no atomics)
@@ -267,8 +275,9 @@ BFSM_HD void gen_pass(const cx<T>* src, cx<T>* dst, const cx<T>* tw, int n, int 
 // BIG: the instantiation that also carries the table-driven radix-7 / 11 / 13 butterflies (13 complex inputs + 13 outputs
 // in registers: 256 VGPRs and a kilobyte of scratch per lane in double precision).  Axes whose factors are 2, 3, 5 only --
 // nearly every box -- run the instantiation without them (round 4; GK::Fft / GK::FftBig).
-template <typename T, bool BIG, int C, class Ctx>
-BFSM_HD void body_gen_fft(const GenFftParams<T>& prm, Ctx& ctx) {
+template <typename T, bool BIG, int C, class Ctx, class P>
+BFSM_HD void body_gen_fft(const P& prm, Ctx& ctx) {
+    constexpr bool BI = gen_bilinear<P>::value;
     const int nx = prm.nx, ny = prm.ny, nz = prm.nz;
     const int axis = prm.axis;
     const int n = axis == 0 ? nx : (axis == 1 ? ny : nz);
@@ -310,6 +319,7 @@ BFSM_HD void body_gen_fft(const GenFftParams<T>& prm, Ctx& ctx) {
     }
     const bool loss_slot = prm.mode == GEN_TAIL2 && (b & 1);
     const cx<T>* inc = loss_slot ? prm.in2 : static_cast<const cx<T>*>(prm.in);
+    if constexpr (BI) { if (prm.mode == GEN_PHASE && (b & 1)) inc = prm.in2; }
     // the global loads are issued four points at a time before any of them is consumed: the trip count is a run-time
     // value, and a rolled loop would pay one full memory latency per point
     constexpr int STEP = GEN_THREADS / C, CH = 4;
@@ -443,8 +453,9 @@ BFSM_HD void gen_plane_axis(cx<T>*& src, cx<T>*& dst, const cx<T>* tw, const int
 // radices 2, 3, 5): the plane [y][z] is contiguous in memory, so the loads and stores are fully coalesced, and a 3-D
 // transform is 2 array passes here + 1 x-pass instead of 3 passes -- 12 array moves per direction instead of 18.
 // grid = (nx planes, batch).  Forward (sign -1): z then y; backward: y then z.  Same load-side fusions as body_gen_fft.
-template <typename T, class Ctx>
-BFSM_HD void body_gen_plane(const GenFftParams<T>& prm, Ctx& ctx) {
+template <typename T, class Ctx, class P>
+BFSM_HD void body_gen_plane(const P& prm, Ctx& ctx) {
+    constexpr bool BI = gen_bilinear<P>::value;
     const int nx = prm.nx, ny = prm.ny, nz = prm.nz;
     const int ix = ctx.bx();
     int b = ctx.by();
@@ -464,6 +475,8 @@ BFSM_HD void body_gen_plane(const GenFftParams<T>& prm, Ctx& ctx) {
     gen_stage_tw<T>(twb, prm.tw_b, prm.sign < 0 ? ny : nz, ctx);
     const size_t plane = (size_t)ny * nz, base = (size_t)ix * plane;
     const size_t in_off = in_moff + (size_t)b * prm.in_bstride;
+    const cx<T>* inc = static_cast<const cx<T>*>(prm.in);
+    if constexpr (BI) { if (prm.mode == GEN_PHASE && (b & 1)) inc = prm.in2; }
     // (iy, iz) of the element this thread touches, advanced by GEN_THREADS elements per step without a division
     const int dy = GEN_THREADS / nz, dz = GEN_THREADS - dy * nz;
     int iy = ctx.tid() / nz, iz = ctx.tid() - iy * nz;
@@ -471,6 +484,7 @@ BFSM_HD void body_gen_plane(const GenFftParams<T>& prm, Ctx& ctx) {
         const size_t idx = base + e;
         cx<T> v = {(T)0, (T)0};
         if (prm.mode == GEN_REAL) v.x = (T) static_cast<const double*>(prm.in)[in_off + idx];
+        else if constexpr (BI) v = inc[in_off + idx];
         else v = static_cast<const cx<T>*>(prm.in)[in_off + idx];
         if (prm.mode == GEN_PRODUCT) v = cmul(v, prm.in2[in_off + idx]);
         else if (prm.mode == GEN_PHASE) {
@@ -633,9 +647,11 @@ BFSM_HD void body_gen_line3(const GenLineParams<T>& prm, Ctx& ctx) {
 // direction d's two planes at batch slots 2d, 2d + 1.
 template <typename T>
 constexpr int gen_plane_maxe() { return (int)((size_t)40 * 1024 / (2 * sizeof(cx<T>)) + GEN_THREADS - 1) / GEN_THREADS; }
-template <typename T, class Ctx>
-BFSM_HD void body_gen_plane_pair(const GenFftParams<T>& prm, Ctx& ctx) {
+// Bilinear form (GenFftBiParams): the conj(alpha) member is formed from in2 (f_hat), read when that sign is stored.
+template <typename T, class Ctx, class P>
+BFSM_HD void body_gen_plane_pair(const P& prm, Ctx& ctx) {
     constexpr int MAXE = gen_plane_maxe<T>();
+    constexpr bool BI = gen_bilinear<P>::value;
     const int nx = prm.nx, ny = prm.ny, nz = prm.nz;
     const int ix = ctx.bx();
     const int mem = ctx.by() / prm.mper, d = ctx.by() - mem * prm.mper;
@@ -673,7 +689,10 @@ BFSM_HD void body_gen_plane_pair(const GenFftParams<T>& prm, Ctx& ctx) {
         int iy = iy0, iz = iz0;
 #pragma unroll
         for (int k = 0; k < MAXE; ++k) {
-            if (ctx.tid() + k * GEN_THREADS < plane) buf0[iy * LSZ + iz] = sgn2 ? cmulc(fr[k], ph[k]) : cmul(fr[k], ph[k]);
+            const int e = ctx.tid() + k * GEN_THREADS;
+            if constexpr (BI) {
+                if (e < plane) buf0[iy * LSZ + iz] = sgn2 ? cmulc(prm.in2[(size_t)mem * prm.in_mstride + base + e], ph[k]) : cmul(fr[k], ph[k]);
+            } else if (e < plane) buf0[iy * LSZ + iz] = sgn2 ? cmulc(fr[k], ph[k]) : cmul(fr[k], ph[k]);
             iy += dy; iz += dz;
             if (iz >= nz) { iz -= nz; ++iy; }
         }
@@ -995,7 +1014,7 @@ struct GenericPipeline {
         }
         ok = ok && dev_copy(phx, hx_) && dev_copy(phy, hy_) && dev_copy(phz, hz_) && dev_copy(dirw, hw) && dev_copy(rdir, hr);
         ok = ok && dev_copy(beta1, b1) && dev_copy(beta2, b2v);
-        ok = ok && (fhat = (cx<T>*)be->alloc((size_t)mb * G * sizeof(cx<T>)));
+        ok = ok && (fhat = (cx<T>*)be->alloc((size_t)(mb > 2 ? mb : 2) * G * sizeof(cx<T>)));   // >= 2: Q(g,f) keeps two spectra
         ok = ok && (qhat = (cx<T>*)be->alloc((size_t)mb * G * sizeof(cx<T>)));
         ok = ok && (tail = (cx<T>*)be->alloc((size_t)2 * max_batch * G * sizeof(cx<T>)));
         ok = ok && (a = (cx<T>*)be->alloc((size_t)mb * 2 * chunk * G * sizeof(cx<T>)));
@@ -1044,10 +1063,21 @@ struct GenericPipeline {
         const size_t lds = ((size_t)2 * n * (C + 1) + n) * sizeof(cx<T>);
         bool big = false;
         for (int r : radix[axis]) big = big || gen_table_radix(r);
-        if (big && C == 8) be->template launch_gen<GK::FftBig8, T>((ncols + C - 1) / C, batch, GEN_THREADS, lds, p);
-        else if (big) be->template launch_gen<GK::FftBig, T>((ncols + C - 1) / C, batch, GEN_THREADS, lds, p);
-        else if (C == 8) be->template launch_gen<GK::Fft8, T>((ncols + C - 1) / C, batch, GEN_THREADS, lds, p);
-        else be->template launch_gen<GK::Fft, T>((ncols + C - 1) / C, batch, GEN_THREADS, lds, p);
+        if (big && C == 8) launch_fft<GK::FftBig8>((ncols + C - 1) / C, batch, lds, p);
+        else if (big) launch_fft<GK::FftBig>((ncols + C - 1) / C, batch, lds, p);
+        else if (C == 8) launch_fft<GK::Fft8>((ncols + C - 1) / C, batch, lds, p);
+        else launch_fft<GK::Fft>((ncols + C - 1) / C, batch, lds, p);
+    }
+    // a GEN_PHASE producer given a second spectrum (in2) is the bilinear form's: its own instantiation (GenFftBiParams)
+    template <GK kind>
+    void launch_fft(int gx, int gy, size_t lds, const GenFftParams<T>& p) {
+        if (p.mode == GEN_PHASE && p.in2) {
+            GenFftBiParams<T> q{};
+            static_cast<GenFftParams<T>&>(q) = p;
+            be->template launch_gen<kind, T>(gx, gy, GEN_THREADS, lds, q);
+        } else {
+            be->template launch_gen<kind, T>(gx, gy, GEN_THREADS, lds, p);
+        }
     }
     int pass_lines(int n) const {
 #ifdef BFSM_GEN_LINES16           // A/B builds (tools only)
@@ -1091,7 +1121,7 @@ struct GenericPipeline {
         p.mode = mode; p.phx = phx; p.phy = phy; p.phz = phz; p.dir0 = dir0; p.beta2 = beta2;
         p.in_bstride = in_bstride; p.out_bstride = out_bstride;
         const size_t lds = ((size_t)2 * ny * (nz + 1) + ny + nz) * sizeof(cx<T>);
-        be->template launch_gen<GK::Plane, T>(nx, batch, GEN_THREADS, lds, p);
+        launch_fft<GK::Plane>(nx, batch, lds, p);
     }
 
     // The fused sequence (plane kernel straight from f_hat, x-line kernel, plane-accumulate kernel: 6 array moves per
@@ -1150,7 +1180,7 @@ struct GenericPipeline {
     // batches of distributions go through the fused sequence together (every launch covers all members); the other
     // sequences take them one after the other
     bool batch_together() const { return fused_ok(); }
-    void gain_chunk_fused(const Chunk& c, bool first, int nb = 1) {
+    void gain_chunk_fused(const Chunk& c, bool first, int nb = 1, const cx<T>* fb = nullptr) {
         const double Gc = (double)G * sizeof(cx<T>);
         // A1', A2' = IFFT_yz(alpha f_hat / G), IFFT_yz(conj(alpha) f_hat / G), straight from f_hat (x stays spectral)
         be->mark(BFSM_K_GAIN_INV, 2.0 * c.n * nb * Gc);
@@ -1162,7 +1192,7 @@ struct GenericPipeline {
         // 0.117 -> 0.133 ms there) -- profiles/r04_generic_fused_ab.txt
         constexpr bool PAIR = sizeof(T) == 8;
 #endif
-        if (!PAIR) plane(fhat, nullptr, a, 2 * c.n * nb, +1, GEN_PHASE, 0, G, c.dir0, 2 * c.n, G, a_mstride());
+        if (!PAIR) plane(fhat, fb, a, 2 * c.n * nb, +1, GEN_PHASE, 0, G, c.dir0, 2 * c.n, G, a_mstride());
         else {
             GenFftParams<T> ki{};
             ki.in = fhat; ki.out = a; ki.nx = nx; ki.ny = ny; ki.nz = nz; ki.axis = 1; ki.sign = +1; ki.C = GEN_C; ki.mode = GEN_PHASE;
@@ -1172,7 +1202,8 @@ struct GenericPipeline {
             for (int i = 0; i < ki.n_radix_b; ++i) ki.radix_b[i] = radix[2][i];
             ki.phx = phx; ki.phy = phy; ki.phz = phz; ki.dir0 = c.dir0;
             ki.mper = c.n; ki.in_mstride = G; ki.out_mstride = a_mstride();
-            be->template launch_gen<GK::PlanePair, T>(nx, c.n * nb, GEN_THREADS, ((size_t)2 * ny * (nz + 1) + ny + nz) * sizeof(cx<T>), ki);
+            ki.in2 = fb;
+            launch_fft<GK::PlanePair>(nx, c.n * nb, ((size_t)2 * ny * (nz + 1) + ny + nz) * sizeof(cx<T>), ki);
         }
         line3(c, nb);
         GenPlaneAccParams<T> kp{};
@@ -1195,27 +1226,49 @@ struct GenericPipeline {
     // f_hat = FFT(f), then the gain term of this shard into qhat   (CUDABoltzmannOperator.cu:131-191)
     // nb > 1 (members at f_dev + m G, their f_hat / Q_hat at fhat / qhat + m G) only where batch_together()
     void gain_partial(const double* f_dev, int nb = 1, bool = true) {
+        spectrum(f_dev, fhat, nb);
+        gain_spectra(nb, nullptr);
+    }
+
+    // out = FFT(f), natural layout
+    void spectrum(const double* f_dev, cx<T>* out, int nb) {
         const double Gc = (double)G * sizeof(cx<T>);
         const bool pl = plane_ok();
         be->mark(BFSM_K_FFT_F, 1.5 * nb * Gc);
-        if (pl) plane(f_dev, nullptr, fhat, nb, -1, GEN_REAL, G, G);
+        if (pl) plane(f_dev, nullptr, out, nb, -1, GEN_REAL, G, G);
         else {
-            pass(f_dev, nullptr, fhat, nb, 2, -1, GEN_REAL, G, G);
-            be->mark(BFSM_K_FFT_F, 2.0 * nb * Gc); pass(fhat, nullptr, fhat, nb, 1, -1, GEN_PLAIN, G, G);
+            pass(f_dev, nullptr, out, nb, 2, -1, GEN_REAL, G, G);
+            be->mark(BFSM_K_FFT_F, 2.0 * nb * Gc); pass(out, nullptr, out, nb, 1, -1, GEN_PLAIN, G, G);
         }
-        be->mark(BFSM_K_FFT_F, 2.0 * nb * Gc); pass(fhat, nullptr, fhat, nb, 0, -1, GEN_PLAIN, G, G);
+        be->mark(BFSM_K_FFT_F, 2.0 * nb * Gc); pass(out, nullptr, out, nb, 0, -1, GEN_PLAIN, G, G);
+    }
+
+    // Bilinear form Q(g,f): as Pipeline::collide_bilinear (g_hat in fhat, f_hat in fhat + G: init reserves two spectra)
+    cx<T>* fhat_b() const { return fhat + G; }
+    void collide_bilinear(double* Q_dev, const double* g_dev, const double* f_dev, bool with_loss) {
+        spectrum(g_dev, fhat, 1);
+        const cx<T>* fb = fhat;
+        if (f_dev != g_dev) { spectrum(f_dev, fhat_b(), 1); fb = fhat_b(); }
+        gain_spectra(1, fb);
+        finish(Q_dev, g_dev, with_loss, 1, false, fb);
+    }
+
+    // the gain term of this shard from fhat (and fb: the conj(alpha) operand of the bilinear form) into qhat
+    void gain_spectra(int nb, const cx<T>* fb) {
+        const double Gc = (double)G * sizeof(cx<T>);
+        const bool pl = plane_ok();
         bool first = true;
         const bool fused = fused_ok(), l3 = line3_ok((size_t)150 * 1024);
         for (const Chunk& c : plan.chunks) {
-            if (fused) { gain_chunk_fused(c, first, nb); first = false; continue; }
+            if (fused) { gain_chunk_fused(c, first, nb, fb); first = false; continue; }
             const int nb2 = 2 * c.n;
             if (l3) {
                 // the (y,z) passes of the inverse transforms first (phase factors on the load side, straight from f_hat), then
                 // the x-line kernel, then the (y,z) passes of the forward transform: 14 array moves (8 with the plane kernel)
                 be->mark(BFSM_K_GAIN_INV, 2.0 * c.n * Gc);
-                if (pl) plane(fhat, nullptr, a, nb2, +1, GEN_PHASE, 0, G, c.dir0);
+                if (pl) plane(fhat, fb, a, nb2, +1, GEN_PHASE, 0, G, c.dir0);
                 else {
-                    pass(fhat, nullptr, a, nb2, 2, +1, GEN_PHASE, 0, G, c.dir0);
+                    pass(fhat, fb, a, nb2, 2, +1, GEN_PHASE, 0, G, c.dir0);
                     be->mark(BFSM_K_GAIN_INV, 0); pass(a, nullptr, a, nb2, 1, +1, GEN_PLAIN, G, G);
                 }
                 line3(c);
@@ -1235,7 +1288,7 @@ struct GenericPipeline {
             // accounting: the SURVEY 8(d) model attributes 2 array passes per direction to this group (the inverse
             // transforms), 3 to the next (product + forward transform) and 1 to the accumulate; the path moves more
             be->mark(BFSM_K_GAIN_INV, 2.0 * c.n * Gc);
-            pass(fhat, nullptr, a, nb2, 0, +1, GEN_PHASE, 0, G, c.dir0);
+            pass(fhat, fb, a, nb2, 0, +1, GEN_PHASE, 0, G, c.dir0);
             if (pl) { be->mark(BFSM_K_GAIN_INV, 0); plane(a, nullptr, a, nb2, +1, GEN_PLAIN, G, G); }
             else {
                 be->mark(BFSM_K_GAIN_INV, 0); pass(a, nullptr, a, nb2, 1, +1, GEN_PLAIN, G, G);
@@ -1263,7 +1316,8 @@ struct GenericPipeline {
     }
 
     // loss term + final inverse transforms + combine   (CUDABoltzmannOperator.cu:193-216)
-    void finish(double* Q_dev, const double* f_dev, bool with_loss = true, int nb = 1, bool = false) {
+    // loss_hat (bilinear form): the spectrum the loss term convolves (f_hat); f_dev is then g, which multiplies it
+    void finish(double* Q_dev, const double* f_dev, bool with_loss = true, int nb = 1, bool = false, const cx<T>* loss_hat = nullptr) {
         const double Gc = (double)G * sizeof(cx<T>);
         cx<T>* tg = tail;                                   // [max_batch][G] gain, then [max_batch][G] loss
         cx<T>* tl = tail + (size_t)max_batch * G;
@@ -1279,7 +1333,7 @@ struct GenericPipeline {
         if (with_loss) {
             // gain and loss term through the same launches: slot s of member m at tail + (s max_batch + m) G
             const size_t half = (size_t)max_batch * G;
-            pass(qhat, fhat, tail, 2 * nb, 0, +1, GEN_TAIL2, 0, half, 0, 2, G, G);
+            pass(qhat, loss_hat ? loss_hat : fhat, tail, 2 * nb, 0, +1, GEN_TAIL2, 0, half, 0, 2, G, G);
             if (pl) { be->mark(BFSM_K_TAIL, 0); plane(tail, nullptr, tail, 2 * nb, +1, GEN_PLAIN, G, G, 0, nb, half, half); }
             else {
                 be->mark(BFSM_K_TAIL, 0); pass(tail, nullptr, tail, 2 * nb, 1, +1, GEN_PLAIN, G, G, 0, nb, half, half);

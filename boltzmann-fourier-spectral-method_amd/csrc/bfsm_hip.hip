@@ -808,6 +808,41 @@ int bfsm_collide(bfsm_handle h, double* Q_dev, const double* f_dev) {
     return bfsm_synchronize(h);
 }
 
+// Bilinear form Q(g,f): F1 of g and of f, the gain kernels with A1' from g_hat and A2' from f_hat, the tail with the loss
+// spectrum f_hat multiplied by g (Pipeline::collide_bilinear / GenericPipeline::collide_bilinear).
+int bfsm_collide_bilinear_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, int with_loss,
+                                        void* stream) {
+    if (!h) return BFSM_ERR_INVALID;
+    BFSM_GUARDED(h,
+        DeviceGuard guard(h->desc.device);
+        int rc = enter(h, guard, stream);
+        if (rc) return rc;
+        if (!g_dev || !f_dev || !Q_dev) return fail(h, BFSM_ERR_INVALID, "null Q, g or f");
+        if (h->desc.flags & BFSM_FLAG_EXACT_REDUCTIONS)
+            return fail(h, BFSM_ERR_UNSUPPORTED, "the bilinear form needs a handle without BFSM_FLAG_EXACT_REDUCTIONS (its antipodal merge assumes g = f)");
+        const double* q0 = Q_dev;
+        const double* q1 = Q_dev + h->G;
+        auto overlaps = [&](const double* a) { return a < q1 && q0 < a + h->G; };
+        if (overlaps(g_dev) || overlaps(f_dev)) return fail(h, BFSM_ERR_INVALID, "Q must not overlap g or f");
+        h->be.begin_eval();
+        h->with([&](auto& p) { p.collide_bilinear(Q_dev, g_dev, f_dev, with_loss != 0); });
+        return leave(h, "bfsm_collide_bilinear");
+    )
+}
+
+int bfsm_collide_bilinear_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, void* stream) {
+    if (!h) return BFSM_ERR_INVALID;
+    if (!h->full_shard)
+        return fail(h, BFSM_ERR_INVALID, "bfsm_collide_bilinear needs a handle that owns all directions; use bfsm_collide_bilinear_partial_async + a sum over the ranks");
+    return bfsm_collide_bilinear_partial_async(h, Q_dev, g_dev, f_dev, 1, stream);
+}
+
+int bfsm_collide_bilinear(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev) {
+    int rc = bfsm_collide_bilinear_async(h, Q_dev, g_dev, f_dev, nullptr);
+    if (rc) return rc;
+    return bfsm_synchronize(h);
+}
+
 int bfsm_synchronize(bfsm_handle h) {
     if (!h) return BFSM_ERR_INVALID;
     BFSM_GUARDED(h,

@@ -348,7 +348,8 @@ struct Pipeline {
         slab_count = plan.segs.size();
         const size_t nslab = slab_count ? slab_count : 1;
         bool ok = true;
-        ok = ok && (fhat = (cx<T>*)be->alloc(nb * G * sizeof(cx<T>)));
+        // at least two spectra: the bilinear form Q(g,f) keeps g_hat and f_hat (collide_bilinear)
+        ok = ok && (fhat = (cx<T>*)be->alloc((nb > 2 ? nb : 2) * G * sizeof(cx<T>)));
         ok = ok && (tg = (cx<T>*)be->alloc(nb * G * sizeof(cx<T>)));
         ok = ok && (tl = (cx<T>*)be->alloc(nb * G * sizeof(cx<T>)));
         ok = ok && (qhat = (cx<T>*)be->alloc(nb * G * sizeof(cx<T>)));
@@ -434,20 +435,49 @@ struct Pipeline {
     // do_reduce = false leaves the slabs un-summed (qhat is not written): for callers that continue with
     // finish(..., from_slabs = true) in the same call and never expose qhat.
     void gain_partial(const double* f_dev, int nb = 1, bool do_reduce = true) {
+        spectrum(f_dev, fhat, nb);
+        gain_spectra(nb, do_reduce, nullptr);
+    }
+
+    // F1: out = FFT(f)  (CUDABoltzmannOperator.cu:133-140), spectral layout
+    void spectrum(const double* f_dev, cx<T>* out, int nb) {
+        const int N = plan.N;
+        const double Gc = (double)plan.G() * cbytes() * nb;
+        TileFwdRealParams<T> pa{f_dev, tg, tw};
+        be->mark(BFSM_K_FFT_F, 1.5 * Gc);
+        be->template launch<K::TileFwdReal, T>(N, nb, 1, pa, N);
+        LineParams<T> pb{tg, out, tw};
+        be->mark(BFSM_K_FFT_F, 2.0 * Gc);
+        be->template launch<K::LineFwd, T>(line_blocks(), nb, 1, pb, N);
+    }
+
+    // Bilinear form Q(g,f) (include/bfsm.h, bfsm_collide_bilinear): A1' from g_hat, A2' from f_hat, loss = g * Re IFFT(beta2
+    // f_hat / G).  One distribution; the faithful mode only (the exact reductions merge antipodes, which assumes g = f); N = 16
+    // takes the plane-tile pipeline (the whole-direction kernels have no room for a second cube).  g_hat in fhat, f_hat in
+    // fhat + G (init reserves two spectra).
+    cx<T>* fhat_b() const { return fhat + plan.G(); }
+    void collide_bilinear(double* Q_dev, const double* g_dev, const double* f_dev, bool with_loss) {
+        spectrum(g_dev, fhat, 1);
+        if (f_dev == g_dev) {     // Q(f,f) through the bilinear kernels: one transform, both operands read the same spectrum
+            const bool fu = fuse_reduce();
+            gain_spectra(1, !fu, fhat);
+            finish(Q_dev, g_dev, with_loss, 1, fu, fhat);
+            return;
+        }
+        spectrum(f_dev, fhat_b(), 1);
+        const bool fu = fuse_reduce();
+        gain_spectra(1, !fu, fhat_b());
+        finish(Q_dev, g_dev, with_loss, 1, fu, fhat_b());
+    }
+
+    // The gain term of this shard from the spectra in fhat (and fhat2 for the bilinear form: the conj(alpha) operand) into qhat
+    void gain_spectra(int nb, bool do_reduce, const cx<T>* fhat2) {
         const int N = plan.N;
         const double Gc = (double)plan.G() * cbytes() * nb;
         const size_t G = plan.G();
         const size_t a_bs = cap * (size_t)a_planes * N * N, s_bs = (slab_count ? slab_count : 1) * G;
         const size_t r_bs = cap * r_per_dir();
         const double hfrac = (double)a_planes / N;                 // share of A' actually stored
-        {   // F1: f_hat  (CUDABoltzmannOperator.cu:133-140)
-            TileFwdRealParams<T> pa{f_dev, tg, tw};
-            be->mark(BFSM_K_FFT_F, 1.5 * Gc);
-            be->template launch<K::TileFwdReal, T>(N, nb, 1, pa, N);
-            LineParams<T> pb{tg, fhat, tw};
-            be->mark(BFSM_K_FFT_F, 2.0 * Gc);
-            be->template launch<K::LineFwd, T>(line_blocks(), nb, 1, pb, N);
-        }
         for (const Chunk& c : plan.chunks) {
             // KA's parallelism is planes x direction groups: keep >= 2 workgroups per CU when only N/2 + 1 planes run
             const int tw_ = target_workgroups(N, max_batch);
@@ -470,7 +500,12 @@ struct Pipeline {
             const int kn_blocks = kn_rides ? 2 * c.n : 0, kn_rows = (kn_blocks + a_planes - 1) / a_planes;
             GainInvParams<T> ka{fhat, a1, a2, phx, phy, phz, tw, c.dir0, c.n, per_group_a, a_bs, a_planes, warm ? 1 : 0};
             be->mark(BFSM_K_GAIN_INV, 2.0 * c.n * Gc * hfrac);
-            if (kn_rides) {                     // KA + guest KN workgroups
+            if (fhat2) {                        // bilinear form (faithful mode only: no Nyquist rows, no GainInvTwo)
+                GainInvBiParams<T> kab{};
+                static_cast<GainInvParams<T>&>(kab) = ka;
+                kab.fhat2 = fhat2;
+                be->template launch<K::GainInv, T>(a_planes, ga, nb, kab, N);
+            } else if (kn_rides) {              // KA + guest KN workgroups
                 GainInvNyqParams<T> kan{ka, rnyq, r_bs, kn_blocks, ga};
                 be->template launch<K::GainInvNyq, T>(a_planes, ga + kn_rows, nb, kan, N);
             } else if (pair_geometry() && !interleaved()) be->template launch<K::GainInvTwo, T>(a_planes, ga, nb, ka, N);
@@ -515,11 +550,13 @@ struct Pipeline {
     // with_loss = false: Q = Re IFFT(qhat) only -- the partial result a rank contributes when the caller sums Q
     // itself (half the bytes of summing Q_hat) and another rank adds the loss term.
     // from_slabs = true: the slab reduce is fused into the first tail kernel (after gain_partial(.., false)).
-    void finish(double* Q_dev, const double* f_dev, bool with_loss = true, int nb = 1, bool from_slabs = false) {
+    // loss_hat (bilinear form): the spectrum the loss term convolves (f_hat); f_dev is then g, which multiplies it.
+    void finish(double* Q_dev, const double* f_dev, bool with_loss = true, int nb = 1, bool from_slabs = false,
+                const cx<T>* loss_hat = nullptr) {
         const int N = plan.N;
         const double Gc = (double)plan.G() * cbytes() * nb;
         const size_t s_bs = (slab_count ? slab_count : 1) * plan.G();
-        TailInvParams<T> ta{qhat, fhat, beta2, tg, (long long)(tl - tg), tw, slab, beta1, segs, from_slabs ? (int)slab_count : -1,
+        TailInvParams<T> ta{qhat, loss_hat ? loss_hat : fhat, beta2, tg, (long long)(tl - tg), tw, slab, beta1, segs, from_slabs ? (int)slab_count : -1,
                             plan.n2stride, s_bs};
         be->mark(BFSM_K_TAIL, ((with_loss ? 4.0 : 2.0) + (from_slabs ? (double)slab_count - 1.0 : 0.0)) * Gc);
         be->template launch<K::TailInv, T>(N, with_loss ? 2 : 1, nb, ta, N);

@@ -46,6 +46,9 @@ public:
     std::string getBackendName() const override { return bfsm_backend_name(); }
     void computeCollision(double* Q, const double* f_in) override;      // device pointers, blocking
     void operator()(double* Q, const double* f_in) override { computeCollision(Q, f_in); }
+    // Bilinear form Q(g,f) (include/bfsm.h, bfsm_collide_bilinear): device pointers, blocking.  Not part of
+    // AbstractCollisionOperator; Q(f,f) is computeCollision(Q, f).
+    void computeCollision(double* Q, const double* g, const double* f);
 
     // Batch of n_batch <= setMaxBatch() distributions, [n_batch][Nvx*Nvy*Nvz] device arrays, one set of launches.
     void computeCollisionBatch(double* Q, const double* f_in, int n_batch);

@@ -43,6 +43,10 @@ void BoltzmannOperator<HIP_Backend>::computeCollision(double* Q, const double* f
     check(bfsm_collide(handle_, Q, f_in), "computeCollision");
 }
 
+void BoltzmannOperator<HIP_Backend>::computeCollision(double* Q, const double* g, const double* f) {
+    check(bfsm_collide_bilinear(handle_, Q, g, f), "computeCollision (bilinear)");
+}
+
 void BoltzmannOperator<HIP_Backend>::computeCollisionBatch(double* Q, const double* f_in, int n_batch) {
     check(bfsm_collide_batch(handle_, Q, f_in, n_batch), "computeCollisionBatch");
 }

@@ -185,10 +185,36 @@ int bfsm_collide_partial_async(bfsm_handle h, double* Q_dev, const double* f_dev
  * library's spectral layout [lx][lz][ly]); the buffer the collective must sum in place. */
 void* bfsm_qhat_buffer(bfsm_handle h, size_t* n_elems, int* precision);
 
+/*
+ * Bilinear form Q(g,f) (new functionality; the presence of these symbols is the capability check, BFSM_VERSION stays 2).
+ * The oracle loop with three changes: A1 is formed from g_hat = FFT(g), A2 from f_hat = FFT(f) (same phase factors as in
+ * Q(f,f)), and the loss is multiplied by g:
+ *     Q(g,f) = Re IFFT(Q_gain_hat[g_hat, f_hat]) - g * Re IFFT(beta2 f_hat / G).
+ * Q(f,f) is the operator of bfsm_collide; Q is linear in each argument; the loss g(v) (beta2 * f)(v) is the rate at which
+ * g-particles at v are scattered by f.  The linearized operator is L_f[h] = Q(f,h) + Q(h,f).  For a rule with
+ * sigma_{s+M/2} == -sigma_s and equal weights (every shipped design) the gain is symmetric in (g,f); for other rules it is
+ * not, and the definition above is what holds.
+ *   - g, f, Q: device pointers to one distribution each (n_batch = 1).  g == f (the same pointer) is allowed; Q must not
+ *     overlap g or f (BFSM_ERR_INVALID).
+ *   - handles with BFSM_FLAG_EXACT_REDUCTIONS (and therefore BFSM_FLAG_HERMITIAN) return BFSM_ERR_UNSUPPORTED and leave Q
+ *     untouched: their antipodal merge assumes g = f.
+ *   - N = 16 handles evaluate it on the plane-tile pipeline (as with BFSM_FLAG_NO_SMALL_PATH): the whole-direction kernels
+ *     have no room for a second cube.
+ *   - the scratch is reserved at bfsm_create (two spectra), so the async forms are allocation-free and can be captured
+ *     into a HIP graph after one evaluation outside a capture, like bfsm_collide_async.
+ * bfsm_collide_bilinear is blocking; _async enqueues on `stream`; _partial_async works on a direction shard like
+ * bfsm_collide_partial_async: Q = Re IFFT(this shard's partial gain) [- loss if with_loss], summed over the ranks by the
+ * caller, exactly one rank passing with_loss != 0.
+ */
+int bfsm_collide_bilinear(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev);
+int bfsm_collide_bilinear_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, void* stream);
+int bfsm_collide_bilinear_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev,
+                                        int with_loss, void* stream);
+
 /* Blocks until everything enqueued by this handle has completed: the work of every stream that was passed to one of
  * its entry points since the previous bfsm_synchronize is waited for (through events the handle recorded itself), not
- * only the most recent one; the 64 most recently added distinct streams are tracked.  The list is cleared whether or
- * not the wait succeeds, so a failure does not affect later calls. */
+ * only the most recent one; every distinct stream is tracked, however many.  The list is cleared whether or not the
+ * wait succeeds, so a failure does not affect later calls. */
 int bfsm_synchronize(bfsm_handle h);
 
 /* Batched 3-D complex transform with the library's own kernels (counterpart of the cufftPlanMany plan,

@@ -28,5 +28,6 @@ print(f"{'vgpr':>5s} {'agpr':>5s} {'scratch B':>9s} {'static LDS':>10s} {'sgpr':
 for r, n in zip(rows, names):
     if "--scratch" in sys.argv and r[3] == 0:
         continue
-    n = re.sub(r"^void bfsm::bfsm_kernel<\(bfsm::(S?K)\)(\d+), (\d+), (\w+),.*", r"\1 \2 N=\3 \4", n)
+    bi = " bilinear" if "BiParams" in n else ""       # the Q(g,f) instantiations (GainInvBiParams / GenFftBiParams)
+    n = re.sub(r"^void bfsm::bfsm_kernel<\(bfsm::(S?K)\)(\d+), (\d+), (\w+),.*", r"\1 \2 N=\3 \4", n) + bi
     print(f"{r[1]:5d} {r[2]:5d} {r[3]:9d} {r[4]:10d} {r[5]:5d}  {n[:100]}")
