@@ -9,9 +9,11 @@
 #include <ucontext.h>
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../boltzmann-fourier-spectral-method_amd/csrc/bfsm_pipeline.hpp"
@@ -381,9 +383,114 @@ int fft3d_t(int N, double* data, int batch, int sign) {
     return be.failed ? 99 : 0;
 }
 
+// Launch recorder of the size-generic path: GenericPipeline's host code runs as it does in the library, every launch is
+// recorded and nothing is executed.  Device pointers are distinct fake addresses that host code never dereferences.
+// mark() / the launch follow HipBackend's pend_kind rule (csrc/bfsm_hip.hip, mark / launch_any): a launch counts in
+// kernel_launches[kind] of bfsm_get_counters when the last mark() before it named a category >= 0, and every launch
+// clears the mark.
+struct RouteRec {
+    int kind, precision, bilinear, mode, gx, gy;
+    long long lds;
+    int cat;
+};
+
+struct RecordingBackend {
+    std::vector<RouteRec> recs;
+    uintptr_t next = (uintptr_t)1 << 32;
+    int pend_kind = -1;
+    void* alloc(size_t bytes) {
+        void* p = reinterpret_cast<void*>(next);
+        next += ((bytes + 4095) & ~(size_t)4095) + 4096;
+        return p;
+    }
+    void release(void*) {}
+    void upload(void*, const void*, size_t) {}
+    void mark(int kind, double) { pend_kind = kind; }
+
+    template <bfsm::GK kind, typename T, class P>
+    void launch_gen(int gx, int gy, int, size_t lds, const P& prm) {
+        if (gx <= 0 || gy <= 0) return;       // launch_any returns before it consumes the mark
+        int mode = -1;
+        if constexpr (std::is_base_of<bfsm::GenFftParams<T>, P>::value) mode = prm.mode;
+        recs.push_back({(int)kind, (int)(sizeof(T) * 8), bfsm::gen_bilinear<P>::value ? 1 : 0, mode, gx, gy, (long long)lds,
+                        pend_kind});
+        pend_kind = -1;
+    }
+};
+
+// What bfsm_hip.hip runs on a size-generic handle for one call of the entry point `op` (see bfsm_emu_gen_routes)
+template <typename T>
+int gen_routes_t(const bfsm_desc* d, int op, int nb, std::vector<RouteRec>& out, int* info) {
+    RecordingBackend be;
+    bfsm::GenericPipeline<T, RecordingBackend> p;
+    std::string err;
+    int rc = p.init(*d, &be, err);
+    if (rc) return rc;
+    info[0] = p.batch_together() ? 1 : 0;
+    info[1] = p.plan.gen_moves;
+    info[2] = p.plane_ok() ? 1 : 0;
+    info[3] = p.fused_ok() ? 1 : 0;
+    double* Q = reinterpret_cast<double*>(be.alloc((size_t)nb * p.G * sizeof(double)));
+    const double* f = reinterpret_cast<const double*>(be.alloc((size_t)nb * p.G * sizeof(double)));
+    const double* g = reinterpret_cast<const double*>(be.alloc(p.G * sizeof(double)));
+    switch (op) {
+        case 0:     // bfsm_collide_partial_async, with_loss = 1 (bfsm_collide on a full handle)
+        case 2:     // ... with_loss = 0
+            p.gain_partial(f, 1, !p.fuse_reduce());
+            p.finish(Q, f, op == 0, 1, p.fuse_reduce());
+            break;
+        case 1:     // bfsm_collide_batch_partial_async, with_loss = 1
+            if (nb < 1 || nb > p.max_batch) { p.destroy(); return BFSM_ERR_INVALID; }
+            if (p.batch_together()) { p.gain_partial(f, nb); p.finish(Q, f, true, nb); }
+            else
+                for (int i = 0; i < nb; ++i) { p.gain_partial(f + (size_t)i * p.G); p.finish(Q + (size_t)i * p.G, f + (size_t)i * p.G, true); }
+            break;
+        case 3:     // bfsm_collide_bilinear_partial_async, with_loss = 1, g != f
+            p.collide_bilinear(Q, g, f, true);
+            break;
+        case 4:     // bfsm_fft3d forward / backward
+        case 5:
+            p.fft3d(reinterpret_cast<bfsm::cx<T>*>(Q), nb, op == 4 ? -1 : +1);
+            break;
+        default:
+            p.destroy();
+            return BFSM_ERR_INVALID;
+    }
+    p.destroy();
+    out = be.recs;
+    return BFSM_OK;
+}
+
 }  // namespace emu
 
 extern "C" {
+
+// Launch record of one call of a size-generic entry point, run by GenericPipeline's own host code with nothing executed.
+// op: 0 bfsm_collide, 1 bfsm_collide_batch (nb members), 2 bfsm_collide_partial_async without the loss term, 3
+// bfsm_collide_bilinear (g != f), 4 / 5 bfsm_fft3d forward / backward (batch nb).  rows (max_rows x 8 ints): GK kind,
+// precision, bilinear params type, mode (-1: a params type without one), grid x, grid y, LDS bytes, counter category (-1:
+// not counted).  launches[BFSM_K_COUNT]: the kernel_launches bfsm_get_counters reports for that call under BFSM_FLAG_PROFILE.
+// info[4]: batch_together(), plan.gen_moves, plane_ok(), fused_ok().  Returns the launch count, or minus a status code.
+int bfsm_emu_gen_routes(const bfsm_desc* d, int op, int nb, int* rows, int max_rows, int* launches, int* info) {
+    std::string err;
+    int rc = bfsm::validate_desc(*d, err);
+    if (rc) return -rc;
+    if (bfsm::fused_grid(*d)) return -BFSM_ERR_UNSUPPORTED;
+    std::vector<emu::RouteRec> recs;
+    rc = d->precision == BFSM_F64 ? emu::gen_routes_t<double>(d, op, nb, recs, info) : emu::gen_routes_t<float>(d, op, nb, recs, info);
+    if (rc) return -rc;
+    for (int k = 0; k < BFSM_K_COUNT; ++k) launches[k] = 0;
+    for (size_t i = 0; i < recs.size(); ++i) {
+        const emu::RouteRec& r = recs[i];
+        if (r.cat >= 0 && r.cat < BFSM_K_COUNT) launches[r.cat] += 1;
+        if ((int)i < max_rows) {
+            int* o = rows + 8 * i;
+            o[0] = r.kind; o[1] = r.precision; o[2] = r.bilinear; o[3] = r.mode; o[4] = r.gx; o[5] = r.gy;
+            o[6] = (int)r.lds; o[7] = r.cat;
+        }
+    }
+    return (int)recs.size();
+}
 
 // Emulated bfsm_gain_partial + bfsm_finish on host arrays.  qhat_out (optional): 2*G doubles, spectral layout
 // [lx][lz][ly].  Q may be NULL to skip the tail.

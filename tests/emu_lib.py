@@ -7,25 +7,41 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
+_LIB512 = None
 
 
 def lib():
     global _LIB
     if _LIB is None:
         subprocess.check_call(["make", "-C", os.path.join(_HERE, "emu"), "-s"])
-        from bfsm import capi
         # BFSM_EMU_LIB: an alternative build of the same emulator (the AddressSanitizer build of tests/emu/Makefile)
-        L = ctypes.CDLL(os.environ.get("BFSM_EMU_LIB") or os.path.join(_HERE, "emu", "libbfsm_emu.so"))
-        dp = ctypes.POINTER(ctypes.c_double)
-        L.bfsm_emu_collide.argtypes = [ctypes.POINTER(capi.Desc), dp, dp, dp]
-        L.bfsm_emu_collide.restype = ctypes.c_int
-        L.bfsm_emu_fft3d.argtypes = [ctypes.c_int, ctypes.c_int, dp, ctypes.c_int, ctypes.c_int]
-        L.bfsm_emu_fft3d.restype = ctypes.c_int
-        ip = ctypes.POINTER(ctypes.c_int)
-        L.bfsm_emu_plan.argtypes = [ctypes.POINTER(capi.Desc), ip, ctypes.c_int, ip, ctypes.c_int, ip]
-        L.bfsm_emu_plan.restype = ctypes.c_int
-        _LIB = L
+        _LIB = _typed(ctypes.CDLL(os.environ.get("BFSM_EMU_LIB") or os.path.join(_HERE, "emu", "libbfsm_emu.so")))
     return _LIB
+
+
+def lib_gpu_groups():
+    """The emulator built with the library's own plane-accumulate grouping (512 workgroups per launch, as on the GPU;
+    lib() asks for 24 so that small cases give every group several directions)."""
+    global _LIB512
+    if _LIB512 is None:
+        subprocess.check_call(["make", "-C", os.path.join(_HERE, "emu"), "-s"])
+        _LIB512 = _typed(ctypes.CDLL(os.path.join(_HERE, "emu", "libbfsm_emu_wgs512.so")))
+    return _LIB512
+
+
+def _typed(L):
+    from bfsm import capi
+    dp = ctypes.POINTER(ctypes.c_double)
+    L.bfsm_emu_collide.argtypes = [ctypes.POINTER(capi.Desc), dp, dp, dp]
+    L.bfsm_emu_collide.restype = ctypes.c_int
+    L.bfsm_emu_fft3d.argtypes = [ctypes.c_int, ctypes.c_int, dp, ctypes.c_int, ctypes.c_int]
+    L.bfsm_emu_fft3d.restype = ctypes.c_int
+    ip = ctypes.POINTER(ctypes.c_int)
+    L.bfsm_emu_plan.argtypes = [ctypes.POINTER(capi.Desc), ip, ctypes.c_int, ip, ctypes.c_int, ip]
+    L.bfsm_emu_plan.restype = ctypes.c_int
+    L.bfsm_emu_gen_routes.argtypes = [ctypes.POINTER(capi.Desc), ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip, ip]
+    L.bfsm_emu_gen_routes.restype = ctypes.c_int
+    return L
 
 
 def make_desc(nv, gl, sph, gamma, b_gamma, L, precision=64, dir_range=(0, 0), max_chunk=0, flags=0, max_batch=0):
@@ -39,14 +55,15 @@ def make_desc(nv, gl, sph, gamma, b_gamma, L, precision=64, dir_range=(0, 0), ma
     return d, keep
 
 
-def collide(f, gl, sph, gamma, b_gamma, L, precision=64, dir_range=(0, 0), max_chunk=0, want_Q=True, flags=0):
+def collide(f, gl, sph, gamma, b_gamma, L, precision=64, dir_range=(0, 0), max_chunk=0, want_Q=True, flags=0, gpu_groups=False):
+    """gpu_groups: run the build with the library's plane-accumulate grouping (lib_gpu_groups)."""
     nv = f.shape[0] if f.shape[0] == f.shape[1] == f.shape[2] else f.shape
     d, keep = make_desc(nv, gl, sph, gamma, b_gamma, L, precision, dir_range, max_chunk, flags)
     f = np.ascontiguousarray(f, dtype=np.float64)
     Q = np.empty_like(f)
     qh = np.empty(f.shape + (2,))
     dp = ctypes.POINTER(ctypes.c_double)
-    rc = lib().bfsm_emu_collide(ctypes.byref(d), f.ctypes.data_as(dp), Q.ctypes.data_as(dp) if want_Q else None,
+    rc = (lib_gpu_groups() if gpu_groups else lib()).bfsm_emu_collide(ctypes.byref(d), f.ctypes.data_as(dp), Q.ctypes.data_as(dp) if want_Q else None,
                                 qh.ctypes.data_as(dp))
     if rc:
         raise RuntimeError(f"bfsm_emu_collide rc={rc}")
@@ -192,3 +209,36 @@ def collide_partial(f, gl, sph, gamma, b_gamma, L, precision=64, dir_range=(0, 0
     if rc:
         raise RuntimeError(f"bfsm_emu_collide_partial rc={rc}")
     return Q
+
+
+# entry points of bfsm_emu_gen_routes
+ROUTE_OPS = {"collide": 0, "batch": 1, "partial": 2, "bilinear": 3, "fft_fwd": 4, "fft_bwd": 5}
+# csrc/bfsm_generic.hpp enum class GK, in order
+GK_NAMES = ("Fft", "Acc", "Combine", "FftBig", "Plane", "Line3", "PlaneAcc", "PlanePair", "Fft8", "FftBig8", "Line38")
+# csrc/bfsm_generic.hpp load-side modes
+GEN_MODES = {-1: None, 0: "PLAIN", 1: "PHASE", 2: "PRODUCT", 3: "REAL", 4: "BETA2", 5: "TAIL2"}
+
+
+def gen_routes(shape, n_gl, n_sph, precision=64, op="collide", nb=1, max_chunk=0, dir_range=(0, 0), max_batch=0):
+    """Launches of one call of a size-generic entry point (op: a key of ROUTE_OPS), recorded by GenericPipeline's own host
+    code with the GPU's plane-accumulate grouping and nothing executed.  Returns (launches, kernel_launches, info):
+    launches = list of dicts (kind, precision, bilinear, mode, grid, lds, cat), kernel_launches = the 6 per-category
+    counts bfsm_get_counters reports under BFSM_FLAG_PROFILE, info = dict(together, gen_moves, plane, fused) of the
+    pipeline (batch_together(), plan.gen_moves, plane_ok(), fused_ok())."""
+    gl = (np.linspace(1.0, 2.0, n_gl), np.ones(n_gl))
+    sph = (np.ones(n_sph), np.zeros(n_sph), np.zeros(n_sph), np.ones(n_sph))
+    d, keep = make_desc(tuple(shape), gl, sph, 0.0, 1.0, 11.0, precision, dir_range, max_chunk, 0, max_batch)
+    cap = 4096
+    rows = (ctypes.c_int * (8 * cap))()
+    kl = (ctypes.c_int * 6)()
+    info = (ctypes.c_int * 4)()
+    n = lib_gpu_groups().bfsm_emu_gen_routes(ctypes.byref(d), ROUTE_OPS[op], nb, rows, cap, kl, info)
+    if n < 0:
+        raise ValueError(f"bfsm_emu_gen_routes rejected {shape} {precision} {op}: rc={-n}")
+    assert n <= cap
+    out = []
+    for i in range(n):
+        r = rows[8 * i:8 * i + 8]
+        out.append(dict(kind=GK_NAMES[r[0]], precision=r[1], bilinear=bool(r[2]), mode=GEN_MODES[r[3]],
+                        grid=(r[4], r[5]), lds=r[6], cat=r[7]))
+    return out, tuple(kl), dict(together=bool(info[0]), gen_moves=info[1], plane=bool(info[2]), fused=bool(info[3]))

@@ -355,13 +355,20 @@ def test_randomised_plans_against_the_oracle(oracle):
     ((16, 8, 6), 5, 6, 64, 1e-12, {}),                       # fused sequence: groups of 15 directions across radial nodes
     ((12, 6, 10), 4, 6, 32, 2e-5, {"max_chunk": 17}),        # ... single precision, ragged chunks
     ((8, 14, 6), 2, 6, 64, 1e-12, {}),                       # x-line kernel between per-axis passes (a radix-7 y axis: no plane kernel)
-    ((100, 4, 6), 1, 6, 64, 1e-12, {}),                      # 100-point x lines (three 16-line buffers still fit)
+    ((100, 4, 6), 1, 6, 64, 1e-12, {}),                      # 100-point x lines: the 8-line x-line kernel (three 16-line buffers would need 83 200 B > 80 KiB)
     ((160, 4, 6), 1, 6, 64, 1e-12, {}),                      # long x lines: 8 lines per workgroup in the x passes and the x-line kernel
     ((4, 14, 160), 1, 6, 64, 1e-12, {}),                     # ... in a z pass (no plane kernel: radix-7 y axis)
     ((154, 4, 4), 1, 6, 64, 1e-12, {}),                      # ... with the table-driven radices (154 = 2 x 7 x 11)
     ((8, 16, 4), 2, 6, 32, 2e-5, {}),                        # single-precision variant
     ((14, 22, 26), 2, 6, 64, 1e-12, {}),                     # radices 7, 11, 13 (table-driven butterflies)
     ((28, 6, 4), 2, 6, 64, 1e-12, {}),                       # 7 behind 4
+    ((200, 4, 4), 1, 6, 32, 2e-5, {}),                       # single precision: the 8-line x-line kernel (nx >= 198)
+    ((154, 4, 4), 1, 6, 32, 2e-5, {}),                       # ... the table-driven radices (16-line passes in fp32)
+    ((28, 6, 4), 2, 6, 32, 2e-5, {}),                        # ... 7 behind 4
+    ((8, 4, 256), 1, 6, 64, 1e-12, {}),                      # plane kernels on 256-point z lines (dy = 1, dz = 0)
+    ((8, 256, 4), 1, 6, 64, 1e-12, {}),                      # ... on 256-point y lines, exactly at the 40 KiB plane cap
+    # the GPU's plane-accumulate grouping (512 workgroups): 6 groups of 5 directions across radial nodes of 6
+    ((100, 4, 6), 5, 6, 64, 1e-12, {"gpu_groups": True}),
 ])
 def test_size_generic_path_matches_oracle(oracle, shape, n_gl, n_sph, prec, tol, kw):
     """Grids outside the fused pipeline's cubes (csrc/bfsm_generic.hpp: one mixed-radix Stockham pass per axis, pointwise
@@ -374,7 +381,7 @@ def test_size_generic_path_matches_oracle(oracle, shape, n_gl, n_sph, prec, tol,
     L = 11.0
     rng_ = kw.get("dir_range")
     Q, qhat = E.collide(f, gl, sph, 0.5, 0.3, L, prec, max_chunk=kw.get("max_chunk", 0), dir_range=rng_ or (0, 0),
-                        want_Q=rng_ is None)
+                        want_Q=rng_ is None, gpu_groups=kw.get("gpu_groups", False))
     Qo, qo = oracle.collide(f, gl, sph, 0.5, 0.3, L, dir_range=rng_, return_qhat=True)
     assert np.abs(qhat - qo).max() <= tol * np.abs(qo).max()
     if rng_ is None:

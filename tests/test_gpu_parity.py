@@ -966,7 +966,8 @@ def _make_box(bfsm, shape, n_gl, n_sph, precision=64, shard=None, max_chunk=0, g
                                                         ((96, 96, 96), 2, 6, 0), ((64, 48, 80), 2, 12, 5),
                                                         ((16, 128, 32), 3, 6, 0), ((20, 36, 50), 3, 12, 7),
                                                         ((28, 22, 26), 2, 6, 0), ((112, 14, 8), 2, 6, 0),
-                                                        # fused sequence, groups of 4 directions across radial nodes
+                                                        # fused sequence, 6 groups of 6 directions, one radial node
+                                                        # each (groups across radial nodes: tests/generic_cases.py)
                                                         ((96, 8, 10), 6, 6, 0),
                                                         # x-line kernel between plane kernels / between per-axis passes
                                                         ((128, 8, 8), 5, 6, 0), ((16, 28, 12), 2, 6, 0)])
