@@ -9,6 +9,7 @@ BFSM_FLAG_PROFILE = 1
 BFSM_FLAG_EXACT_REDUCTIONS = 2
 BFSM_FLAG_HERMITIAN = 4
 BFSM_FLAG_NO_SMALL_PATH = 8
+BFSM_FLAG_CONSERVE = 16
 KERNEL_NAMES = ("fft_f", "gain_inv", "gain_line", "gain_fwd", "reduce", "tail")
 K_COUNT = len(KERNEL_NAMES)
 
@@ -18,6 +19,7 @@ EXPORTED_SYMBOLS = (
     "bfsm_qhat_buffer",
     "bfsm_synchronize", "bfsm_fft3d", "bfsm_get_counters", "bfsm_destroy", "bfsm_last_error", "bfsm_backend_name",
     "bfsm_version", "bfsm_collide_bilinear", "bfsm_collide_bilinear_async", "bfsm_collide_bilinear_partial_async",
+    "bfsm_conserve_async",
 )
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -101,6 +103,8 @@ def load_library(path=None):
     L.bfsm_collide_bilinear_async.restype = ctypes.c_int
     L.bfsm_collide_bilinear_partial_async.argtypes = [vp, vp, vp, vp, ctypes.c_int, vp]
     L.bfsm_collide_bilinear_partial_async.restype = ctypes.c_int
+    L.bfsm_conserve_async.argtypes = [vp, vp, ctypes.c_int, vp]
+    L.bfsm_conserve_async.restype = ctypes.c_int
     L.bfsm_qhat_buffer.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
     L.bfsm_qhat_buffer.restype = vp
     L.bfsm_synchronize.argtypes = [vp]

@@ -67,6 +67,11 @@ class HIPBoltzmannOperator:
         """N = 16: use (default) or avoid the whole-direction kernels for single evaluations (BFSM_FLAG_NO_SMALL_PATH)."""
         self._flags = (self._flags & ~capi.BFSM_FLAG_NO_SMALL_PATH) | (0 if on else capi.BFSM_FLAG_NO_SMALL_PATH)
 
+    def setConservation(self, on=True):
+        """Conservative projection of every Q this handle writes (BFSM_FLAG_CONSERVE): Q -> PQ with zero discrete mass,
+        momentum and energy.  Default off."""
+        self._flags = (self._flags | capi.BFSM_FLAG_CONSERVE) if on else (self._flags & ~capi.BFSM_FLAG_CONSERVE)
+
     def getBackendName(self):
         return (self._lib or capi.load_library()).bfsm_backend_name().decode()
 
@@ -190,6 +195,16 @@ class HIPBoltzmannOperator:
         self._require(f_in, Q)
         self._check(self._lib.bfsm_collide_partial_async(self._h, _ptr(Q), _ptr(f_in), 1 if with_loss else 0,
                                                          ctypes.c_void_p(stream)))
+
+    def conserve(self, Q, n_batch=1, stream=0):
+        """Q := PQ in place for n_batch consecutive distributions (bfsm_conserve_async; any handle, flag or not), enqueued on
+        `stream`."""
+        if self._h is None:
+            raise RuntimeError("initialize() has not been called")
+        G = self.Nvx * self.Nvy * self.Nvz
+        if not (Q.is_cuda and Q.element_size() == 8 and Q.is_contiguous() and Q.numel() == int(n_batch) * G):
+            raise ValueError("Q must be a contiguous float64 CUDA tensor with n_batch*Nvx*Nvy*Nvz elements")
+        self._check(self._lib.bfsm_conserve_async(self._h, _ptr(Q), int(n_batch), ctypes.c_void_p(stream)))
 
     def qhatBuffer(self):
         """(device pointer, n_elems, precision) of the partial Q_gain_hat owned by the handle."""

@@ -11,6 +11,7 @@
 
 #include "bfsm_pipeline.hpp"
 #include "bfsm_generic.hpp"
+#include "bfsm_conserve.hpp"
 
 #ifndef BFSM_F32_N64_WAVES
 #define BFSM_F32_N64_WAVES 4
@@ -406,6 +407,16 @@ __global__ void __launch_bounds__(SMALL_THREADS) bfsm_small_kernel(const P prm) 
     else if constexpr (kind == SK::Reduce) body_small_reduce<T>(prm, ctx);
 }
 
+// conservative projection (bfsm_conserve.hpp): 256 threads, 10 KiB of LDS
+template <CK kind>
+__global__ void __launch_bounds__(CONS_THREADS) bfsm_cons_kernel(const ConsParams prm) {
+    extern __shared__ __align__(16) unsigned char bfsm_smem[];
+    DevCtx ctx{bfsm_smem};
+    if constexpr (kind == CK::Moments) body_cons_moments(prm, ctx);
+    else if constexpr (kind == CK::Apply) body_cons_apply(prm, ctx);
+    else if constexpr (kind == CK::Small) body_cons_small(prm, ctx);
+}
+
 // ---- HIP backend -----------------------------------------------------------------------------------------------
 struct HipBackend {
     hipStream_t stream = nullptr;
@@ -494,6 +505,12 @@ struct HipBackend {
                    (size_t)160 * 1024);
     }
 
+    template <CK kind>
+    void launch_cons(int gx, int gy, const ConsParams& prm) {
+        static std::atomic<unsigned long long> opted{0};
+        launch_any(reinterpret_cast<const void*>(bfsm_cons_kernel<kind>), gx, gy, 1, CONS_THREADS, CONS_LDS_BYTES, &prm, opted);
+    }
+
     template <K kind, typename T, class P>
     void launch(int gx, int gy, int gz, const P& prm, int N) {
         if (gx <= 0 || gy <= 0 || gz <= 0) return;
@@ -527,6 +544,7 @@ struct bfsm_plan {
     bfsm::Pipeline<float, bfsm::HipBackend>* p32 = nullptr;
     bfsm::GenericPipeline<double, bfsm::HipBackend>* g64 = nullptr;   // grids outside the fused pipeline's sizes
     bfsm::GenericPipeline<float, bfsm::HipBackend>* g32 = nullptr;
+    bfsm::Conserver<bfsm::HipBackend>* cons = nullptr;   // conservative projection (every handle; BFSM_FLAG_CONSERVE)
     bfsm::PlanInfo info;
     size_t G = 0;
     // calls fn(pipeline) on whichever of the four pipelines this handle owns
@@ -628,6 +646,10 @@ static int create_impl(const bfsm_desc* desc, bfsm_handle* out, bfsm_plan*& h) {
         rc = h->p32->init(*desc, &h->be, err);
         h->info = h->p32->plan;
     }
+    if (rc == BFSM_OK) {
+        h->cons = new bfsm::Conserver<bfsm::HipBackend>();
+        rc = h->cons->init(*desc, &h->be, err);
+    }
     // the descriptor's host arrays are not referenced after create
     h->desc.gl_nodes = h->desc.gl_wts = h->desc.sph_wts = h->desc.sx = h->desc.sy = h->desc.sz = nullptr;
     h->full_shard = h->info.full_begin == 0 && h->info.full_end == (long long)desc->n_gl * desc->n_sph;
@@ -697,6 +719,14 @@ static int leave(bfsm_plan* h, const char* where) {
     return BFSM_OK;
 }
 
+// BFSM_FLAG_CONSERVE: the entry points that write Q project it (bfsm_conserve.hpp) behind the pipeline's launches of the call,
+// on the same stream.  The projection reads Q in 16-byte pairs, so Q must be 16-byte aligned (hipMalloc / torch allocations are).
+static bool conserving(const bfsm_plan* h) { return (h->desc.flags & BFSM_FLAG_CONSERVE) != 0; }
+static int check_cons_q(bfsm_plan* h, const double* Q_dev) {
+    if (((uintptr_t)Q_dev & 15) != 0) return fail(h, BFSM_ERR_INVALID, "the conservative projection needs a 16-byte aligned Q");
+    return BFSM_OK;
+}
+
 int bfsm_gain_partial(bfsm_handle h, const double* f_dev, void* stream) {
     if (!h) return BFSM_ERR_INVALID;
     BFSM_GUARDED(h,
@@ -717,7 +747,9 @@ int bfsm_finish(bfsm_handle h, double* Q_dev, const double* f_dev, void* stream)
         int rc = enter(h, g, stream);
         if (rc) return rc;
         if (!f_dev || !Q_dev) return fail(h, BFSM_ERR_INVALID, "null f or Q");
+        if (conserving(h) && (rc = check_cons_q(h, Q_dev))) return rc;
         h->with([&](auto& p) { p.finish(Q_dev, f_dev); });
+        if (conserving(h)) h->cons->apply(Q_dev, 1);
         return leave(h, "bfsm_finish");
     )
 }
@@ -729,7 +761,9 @@ int bfsm_finish_partial(bfsm_handle h, double* Q_dev, const double* f_dev, int w
         int rc = enter(h, g, stream);
         if (rc) return rc;
         if (!f_dev || !Q_dev) return fail(h, BFSM_ERR_INVALID, "null f or Q");
+        if (conserving(h) && (rc = check_cons_q(h, Q_dev))) return rc;
         h->with([&](auto& p) { p.finish(Q_dev, f_dev, with_loss != 0); });
+        if (conserving(h)) h->cons->apply(Q_dev, 1);
         return leave(h, "bfsm_finish_partial");
     )
 }
@@ -745,6 +779,7 @@ int bfsm_collide_batch_partial_async(bfsm_handle h, double* Q_dev, const double*
         h->with([&](auto& p) { cap = p.max_batch; });
         if (n_batch < 1 || n_batch > cap)
             return fail(h, BFSM_ERR_INVALID, "n_batch must be in [1, max_batch of the descriptor]");
+        if (conserving(h) && (rc = check_cons_q(h, Q_dev))) return rc;
         h->be.begin_eval();
         if (h->g64 || h->g32) {      // size-generic path: all members through every launch of the fused sequence, else one by one
             bool together = false;
@@ -760,6 +795,7 @@ int bfsm_collide_batch_partial_async(bfsm_handle h, double* Q_dev, const double*
                 const bool fu = p.fuse_reduce(); p.gain_partial(f_dev, n_batch, !fu); p.finish(Q_dev, f_dev, with_loss != 0, n_batch, fu);
             });
         }
+        if (conserving(h)) h->cons->apply(Q_dev, n_batch);
         return leave(h, "bfsm_collide_batch");
     )
 }
@@ -790,6 +826,7 @@ int bfsm_collide_partial_async(bfsm_handle h, double* Q_dev, const double* f_dev
         int rc = enter(h, g, stream);
         if (rc) return rc;
         if (!f_dev || !Q_dev) return fail(h, BFSM_ERR_INVALID, "null f or Q");
+        if (conserving(h) && (rc = check_cons_q(h, Q_dev))) return rc;
         h->be.begin_eval();
         // gain kernels, then the tail; with few slabs the reduce is fused into its first kernel (qhat is not written then)
         h->with([&](auto& p) {
@@ -798,6 +835,7 @@ int bfsm_collide_partial_async(bfsm_handle h, double* Q_dev, const double* f_dev
             p.gain_partial(f_dev, 1, !fu);
             p.finish(Q_dev, f_dev, with_loss != 0, 1, fu);
         });
+        if (conserving(h)) h->cons->apply(Q_dev, 1);
         return leave(h, "bfsm_collide_partial");
     )
 }
@@ -824,8 +862,10 @@ int bfsm_collide_bilinear_partial_async(bfsm_handle h, double* Q_dev, const doub
         const double* q1 = Q_dev + h->G;
         auto overlaps = [&](const double* a) { return a < q1 && q0 < a + h->G; };
         if (overlaps(g_dev) || overlaps(f_dev)) return fail(h, BFSM_ERR_INVALID, "Q must not overlap g or f");
+        if (conserving(h) && (rc = check_cons_q(h, Q_dev))) return rc;
         h->be.begin_eval();
         h->with([&](auto& p) { p.collide_bilinear(Q_dev, g_dev, f_dev, with_loss != 0); });
+        if (conserving(h)) h->cons->apply(Q_dev, 1);
         return leave(h, "bfsm_collide_bilinear");
     )
 }
@@ -841,6 +881,23 @@ int bfsm_collide_bilinear(bfsm_handle h, double* Q_dev, const double* g_dev, con
     int rc = bfsm_collide_bilinear_async(h, Q_dev, g_dev, f_dev, nullptr);
     if (rc) return rc;
     return bfsm_synchronize(h);
+}
+
+// Q := P Q in place for n_batch consecutive arrays, any handle (the kernels of the BFSM_FLAG_CONSERVE route: bitwise the same)
+int bfsm_conserve_async(bfsm_handle h, double* Q_dev, int n_batch, void* stream) {
+    if (!h) return BFSM_ERR_INVALID;
+    BFSM_GUARDED(h,
+        DeviceGuard g(h->desc.device);
+        int rc = enter(h, g, stream);
+        if (rc) return rc;
+        if (!Q_dev) return fail(h, BFSM_ERR_INVALID, "null Q");
+        if (n_batch < 1 || n_batch > h->cons->max_batch)
+            return fail(h, BFSM_ERR_INVALID, "n_batch must be in [1, max_batch of the descriptor]");
+        if ((rc = check_cons_q(h, Q_dev))) return rc;
+        h->be.begin_eval();
+        h->cons->apply(Q_dev, n_batch);
+        return leave(h, "bfsm_conserve");
+    )
 }
 
 int bfsm_synchronize(bfsm_handle h) {
@@ -895,7 +952,7 @@ int bfsm_get_counters(bfsm_handle h, bfsm_counters* out) {
     c.n_chunks = (int)h->info.chunks.size();
     c.chunk_dirs = h->info.largest_chunk;
     c.n_dirs = h->info.n_dirs();
-    c.moved_bytes_per_eval = bfsm::moved_bytes_per_eval(h->info);
+    c.moved_bytes_per_eval = bfsm::moved_bytes_per_eval(h->info) + (conserving(h) ? h->cons->moved_bytes() : 0.0);
     c.exact_reductions = h->info.exact_reductions ? 1 : 0;
     c.antipodal_merged = h->info.antipodal ? 1 : 0;
     if (h->be.profile && !h->be.recs.empty()) {
@@ -926,6 +983,7 @@ int bfsm_destroy(bfsm_handle h) {
     if (h->p32) { h->p32->destroy(); delete h->p32; }
     if (h->g64) { h->g64->destroy(); delete h->g64; }
     if (h->g32) { h->g32->destroy(); delete h->g32; }
+    if (h->cons) { h->cons->destroy(); delete h->cons; }
     h->be.destroy_events();
     for (auto& pe : h->pending) (void)hipEventDestroy(pe.ev);
     for (hipEvent_t ev : h->spare_events) (void)hipEventDestroy(ev);

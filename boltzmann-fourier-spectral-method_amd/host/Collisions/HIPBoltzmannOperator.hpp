@@ -41,6 +41,8 @@ public:
         if (on) flags_ |= BFSM_FLAG_EXACT_REDUCTIONS | (hermitian ? BFSM_FLAG_HERMITIAN : 0);
     }
     void setMaxBatch(int n) { max_batch_ = n; }
+    // Conservative projection of every Q the operator writes (include/bfsm.h: BFSM_FLAG_CONSERVE).
+    void setConservation(bool on) { flags_ = on ? (flags_ | BFSM_FLAG_CONSERVE) : (flags_ & ~BFSM_FLAG_CONSERVE); }
 
     void initialize() override;
     std::string getBackendName() const override { return bfsm_backend_name(); }
@@ -66,6 +68,8 @@ public:
     int collidePartialStatus(double* Q, const double* f_in, bool with_loss, void* stream = nullptr) noexcept;
     int collideBatchPartialStatus(double* Q, const double* f_in, int n_batch, bool with_loss, void* stream = nullptr) noexcept;
     const char* lastError() const noexcept;
+    // Q := PQ in place for n_batch consecutive device arrays (bfsm_conserve_async), enqueued on `stream`; any handle.
+    void conserve(double* Q, int n_batch = 1, void* stream = nullptr);
     void* qhatBuffer(size_t* n_elems, int* precision) const;
     void synchronize();
     bfsm_counters counters() const;

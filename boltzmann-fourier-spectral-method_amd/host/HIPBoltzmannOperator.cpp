@@ -81,6 +81,10 @@ int BoltzmannOperator<HIP_Backend>::collideBatchPartialStatus(double* Q, const d
 
 const char* BoltzmannOperator<HIP_Backend>::lastError() const noexcept { return bfsm_last_error(handle_); }
 
+void BoltzmannOperator<HIP_Backend>::conserve(double* Q, int n_batch, void* stream) {
+    check(bfsm_conserve_async(handle_, Q, n_batch, stream), "conserve");
+}
+
 void* BoltzmannOperator<HIP_Backend>::qhatBuffer(size_t* n_elems, int* precision) const {
     return bfsm_qhat_buffer(handle_, n_elems, precision);
 }

@@ -2,7 +2,7 @@
 // of the collision operator; the reference stops at a single evaluation of Q).  SSP-RK3 (Shu-Osher) from the BKW
 // state at t0 to t1 with f resident on the device between evaluations; reports the error against the exact BKW
 // solution, mass / energy drift and the entropy at both ends.  Flags: --Nv --Ns --Ngl --t0 --t1 --steps
-// --exact-reductions --hermitian --design-dir.
+// --exact-reductions --hermitian --conserve (BFSM_FLAG_CONSERVE: the conservative projection of Q) --design-dir.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -48,7 +48,7 @@ static void bkw(int Nv, double L, double t, std::vector<double>& f) {
 int main(int argc, char** argv) {
     int Nv = 32, Ns = 32, Ngl = 16, steps = 10;
     double t0 = 5.5, t1 = 6.5;
-    bool exact = false, hermitian = false;
+    bool exact = false, hermitian = false, conserve = false;
     std::string design_dir;
     for (int i = 1; i < argc; ++i) {
         auto val = [&](const char* name) -> const char* {
@@ -66,6 +66,7 @@ int main(int argc, char** argv) {
         else if ((v = val("--design-dir"))) design_dir = v;
         else if (std::strcmp(argv[i], "--exact-reductions") == 0) exact = true;
         else if (std::strcmp(argv[i], "--hermitian") == 0) exact = hermitian = true;
+        else if (std::strcmp(argv[i], "--conserve") == 0) conserve = true;
         else { std::cerr << "error: unknown argument " << argv[i] << "\n"; return EXIT_FAILURE; }
     }
     if (!design_dir.empty()) SphericalDesign::setDataDirectory(design_dir);
@@ -79,6 +80,7 @@ int main(int argc, char** argv) {
     BoltzmannOperator<HIP_Backend> op(std::make_shared<GaussLegendreQuadrature>(Ngl, 0, R),
                                       std::make_shared<SphericalDesign>(Ns), Nv, Nv, Nv, gamma, b_gamma, L);
     op.setExactReductions(exact, hermitian);
+    op.setConservation(conserve);
     op.initialize();
 
     double *f, *f1, *f2, *Q;
@@ -99,6 +101,7 @@ int main(int argc, char** argv) {
     HIP_OR_DIE(hipMemcpy(f_h.data(), f, G * sizeof(double), hipMemcpyDeviceToHost));
 
     double l2 = 0, linf = 0, m0 = 0, m1 = 0, e0 = 0, e1 = 0, h0 = 0, h1 = 0;
+    double p0[3] = {0, 0, 0}, p1[3] = {0, 0, 0};
     for (int i = 0; i < Nv; ++i)
         for (int j = 0; j < Nv; ++j)
             for (int k = 0; k < Nv; ++k) {
@@ -107,6 +110,8 @@ int main(int argc, char** argv) {
                 const double v2 = vx * vx + vy * vy + vz * vz, d = std::abs(f_h[idx] - f_exact[idx]);
                 l2 += d * d; linf = std::max(linf, d);
                 m0 += f0[idx]; m1 += f_h[idx]; e0 += f0[idx] * v2; e1 += f_h[idx] * v2;
+                const double v[3] = {vx, vy, vz};
+                for (int a = 0; a < 3; ++a) { p0[a] += f0[idx] * v[a]; p1[a] += f_h[idx] * v[a]; }
                 if (f0[idx] > 0) h0 += f0[idx] * std::log(f0[idx]);
                 if (f_h[idx] > 0) h1 += f_h[idx] * std::log(f_h[idx]);
             }
@@ -116,6 +121,8 @@ int main(int argc, char** argv) {
               << "L2 error vs exact BKW: " << std::sqrt(l2 * dv3) << "\nLinf error: " << linf
               << "\nrelative mass drift: " << std::abs(m1 - m0) / m0 << "\nrelative energy drift: " << std::abs(e1 - e0) / e0
               << "\nentropy: " << h0 * dv3 << " -> " << h1 * dv3 << "\n";
+    const double dp = std::sqrt((p1[0] - p0[0]) * (p1[0] - p0[0]) + (p1[1] - p0[1]) * (p1[1] - p0[1]) + (p1[2] - p0[2]) * (p1[2] - p0[2]));
+    std::cout << "momentum drift |p1 - p0| / m0: " << dp / m0 << "\n";
     for (double* p : {f, f1, f2, Q}) HIP_OR_DIE(hipFree(p));
     return 0;
 }

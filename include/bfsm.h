@@ -76,7 +76,21 @@ enum {
     /* N = 16 only: do not use the whole-direction kernels (a direction kept in one workgroup's LDS, two launches
      * per evaluation) for single evaluations; the plane-tile pipeline of the larger grids is used instead.  Same
      * results up to rounding order; for comparisons and tests. */
-    BFSM_FLAG_NO_SMALL_PATH = 8
+    BFSM_FLAG_NO_SMALL_PATH = 8,
+    /* Conservative spectral method (Gamba & Tharkabhushanam, J. Comput. Phys. 2009; new functionality, INTEGRATION.md
+     * section 6): every entry point that writes Q writes PQ instead -- bfsm_collide*, bfsm_collide_batch*, bfsm_finish,
+     * bfsm_finish_partial, bfsm_collide_partial_async, bfsm_collide_batch_partial_async and bfsm_collide_bilinear*.  P is the
+     * L2-orthogonal projection onto the grid functions with zero discrete mass, momentum and energy:
+     *     PQ = Q - sum_k (<psi_k, Q> / <psi_k, psi_k>) psi_k,   psi = {1, vx, vy, vz, |v|^2 - c},  c = mean of |v|^2 over the grid,
+     * <a,b> = sum over the G grid points (the grid is symmetric on every axis, so the basis is orthogonal).  P is fixed and
+     * linear: on the partial forms it is applied to each rank's share and the caller's sum is P of the whole Q; batches are
+     * projected member by member.  Always computed in fp64 (also on BFSM_F32 handles), bitwise reproducible, allocation-free.
+     * Combines with the exact / Hermitian modes and the N = 16 path.  bfsm_qhat_buffer() (spectral, before the finish) is not
+     * projected.  For the bilinear form P is applied to Q(g,f) itself: Q(g,f) alone conserves only mass in the continuum,
+     * so PQ(g,f) is the part of Q(g,f) orthogonal to the invariants, and the symmetric sum L_f[h] = PQ(f,h) + PQ(h,f) is
+     * exactly P of the linearized operator (the Jacobian of P o Q).  Q must be 16-byte aligned (BFSM_ERR_INVALID otherwise).
+     * Libraries without this feature ignore the bit: the presence of bfsm_conserve_async is the capability check. */
+    BFSM_FLAG_CONSERVE = 16
 };
 
 typedef struct bfsm_plan* bfsm_handle;
@@ -210,6 +224,12 @@ int bfsm_collide_bilinear(bfsm_handle h, double* Q_dev, const double* g_dev, con
 int bfsm_collide_bilinear_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, void* stream);
 int bfsm_collide_bilinear_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev,
                                         int with_loss, void* stream);
+
+/* Q := PQ in place (the projection of BFSM_FLAG_CONSERVE, by the same kernels: bitwise the same result) for n_batch
+ * consecutive arrays of G doubles, 1 <= n_batch <= max_batch, on any handle with or without the flag; enqueued on `stream`
+ * like the other _async entry points (allocation-free, graph-capturable).  Null or misaligned Q, bad n_batch:
+ * BFSM_ERR_INVALID. */
+int bfsm_conserve_async(bfsm_handle h, double* Q_dev, int n_batch, void* stream);
 
 /* Blocks until everything enqueued by this handle has completed: the work of every stream that was passed to one of
  * its entry points since the previous bfsm_synchronize is waited for (through events the handle recorded itself), not
