@@ -4,7 +4,8 @@ tests/bilinear_ref.py restates the definition in numpy; it is pinned here agains
 The kernel bodies and launch sequences of the bilinear form then run under the host lock-step emulator
 (tests/emu/bfsm_emu_bilinear.cpp, built into its own library with the flags of tests/emu/Makefile) and are compared with
 that restatement on every route: the fused cubes (N = 16 on the plane-tile pipeline), the three sequences of the
-size-generic path, direction shards, and g = f against the emulated Q(f,f).
+size-generic path, direction shards, and g = f against the emulated Q(f,f).  The case table of the GPU suite's fused cubes
+(tests/bilinear_cases.py) is checked against fused_grid() and the library's plan.
 """
 import ctypes
 import os
@@ -14,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import bilinear_cases as BC
 import bilinear_ref as BR
 import emu_lib as E
 
@@ -58,10 +60,11 @@ def lib():
     return _LIB
 
 
-def emu_bilinear(g, f, gl, sph, gamma, b_gamma, L, precision=64, dir_range=(0, 0), with_loss=True, flags=0, same=False):
+def emu_bilinear(g, f, gl, sph, gamma, b_gamma, L, precision=64, dir_range=(0, 0), with_loss=True, flags=0, same=False,
+                 max_chunk=0):
     """same=True passes f's buffer as g (the g == f pointer case of the C-ABI)."""
     nv = f.shape[0] if f.shape[0] == f.shape[1] == f.shape[2] else f.shape
-    d, keep = E.make_desc(nv, gl, sph, gamma, b_gamma, L, precision, dir_range, 0, flags)
+    d, keep = E.make_desc(nv, gl, sph, gamma, b_gamma, L, precision, dir_range, max_chunk, flags)
     f = np.ascontiguousarray(f, dtype=np.float64)
     g = f if same else np.ascontiguousarray(g, dtype=np.float64)
     Q = np.empty_like(f)
@@ -139,6 +142,29 @@ def test_fused_cubes_match_reference(oracle, nv, prec, tol, flags):
     assert _rel(Q, ref) <= tol
 
 
+@pytest.mark.parametrize("nv,prec,n_gl,n_dir,max_chunk", [
+    (40, 64, 1, 3, 0), (64, 64, 1, 3, 0), (80, 64, 1, 3, 0), (96, 64, 1, 3, 0),
+    (40, 32, 1, 3, 0), (64, 32, 1, 3, 0), (80, 32, 1, 3, 0), (96, 32, 1, 3, 0),
+    pytest.param(128, 64, 1, 3, 0, marks=pytest.mark.slow), pytest.param(128, 32, 1, 3, 0, marks=pytest.mark.slow),
+    (64, 32, 2, 7, 2), (96, 64, 2, 7, 2),     # chunks of 2 directions, across the radial-node boundary at 7
+])
+def test_larger_fused_cubes_match_reference(nv, prec, n_gl, n_dir, max_chunk):
+    """The fused cubes of test_fused_cubes_match_reference from N = 40 up, where KA re-reads planes, splits its exchange
+    or interleaves its scratch (tests/bilinear_cases.py).  Inputs of their own: random g and f, a rule without antipodal
+    symmetry and gamma != 0 (the cases above keep theirs and their bounds).  Bounds: the GPU suite's, 1e-12 in fp64 and
+    5e-6 in fp32."""
+    rng = np.random.default_rng(1)
+    g = rng.random((nv, nv, nv)) + 0.1
+    f = rng.random((nv, nv, nv)) + 0.1
+    gl = (np.array([2.5, 7.0])[:n_gl], np.array([3.0, 2.0])[:n_gl])
+    sph = BR.random_rule(n_dir, seed=nv)
+    Q = emu_bilinear(g, f, gl, sph, 0.5, 0.3, 11.0, prec, max_chunk=max_chunk)
+    ref = BR.collide_bilinear(g, f, gl, sph, 0.5, 0.3, 11.0)
+    err = _rel(Q, ref)
+    print(f"N={nv} fp{prec} {n_gl}x{n_dir} max_chunk={max_chunk}: max rel err {err:.2e}")
+    assert err <= (1e-12 if prec == 64 else 5e-6)
+
+
 @pytest.mark.parametrize("shape,prec,tol", [
     ((16, 8, 6), 64, 1e-12),      # fused sequence (plane-pair kernel in double precision)
     ((12, 6, 10), 32, 1e-4),      # fused sequence, single precision (one plane workgroup per sign)
@@ -186,6 +212,50 @@ def test_exact_reduction_handles_are_refused():
     gl = (np.array([3.0]), np.array([1.0]))
     with pytest.raises(RuntimeError, match="rc=2"):
         emu_bilinear(g, f, gl, BR.random_rule(4), 0.0, 0.3, 11.0, flags=2)
+
+
+# ---- the fused-cube case table of the GPU suite (tests/bilinear_cases.py) -----------------------------------------
+
+def _pipeline_text():
+    return open(os.path.join(PKG, "csrc", "bfsm_pipeline.hpp")).read()
+
+
+def test_every_fused_cube_has_a_bilinear_gpu_case():
+    """Every cube size of fused_grid() in both precisions has exactly one case, and nothing else does: a new fused size
+    cannot slip in without a GPU case."""
+    sizes = BC.fused_sizes_of_pipeline(_pipeline_text())
+    assert 16 in sizes and 128 in sizes, sizes
+    required = {(n, p) for n in sizes for p in (64, 32)}
+    declared = [(c.n, c.prec) for c in BC.CUBES]
+    assert len(declared) == len(set(declared)), "a (N, precision) pair declared twice"
+    assert not required - set(declared), f"fused cubes without a bilinear GPU case: {sorted(required - set(declared))}"
+    assert not set(declared) - required, f"cases that are not fused cubes: {sorted(set(declared) - required)}"
+    for c in BC.CUBES:
+        assert c.geometry and c.n_gl >= 1 and c.n_sph >= 3, c
+
+
+def test_launch_variants_take_their_declared_plan():
+    """Each variant's chunks and slabs under the library's own make_plan, and so the reduce route: the separate Reduce
+    launch above fuse_reduce()'s slab limit, the reduce fused into the tail at or below it.  The chunked variants cross a
+    radial-node boundary inside a chunk; every size has one variant of each route."""
+    limit = int(re.search(r"bool fuse_reduce\(\) const \{ return slab_count <= (\d+); \}", _pipeline_text()).group(1))
+    routes = {}
+    for v in BC.VARIANTS:
+        c = BC.cube(v.n, v.prec)
+        chunks, segs = E.plan(v.n, c.n_gl, c.n_sph, v.prec, max_chunk=v.max_chunk)
+        assert (len(chunks), len(segs)) == (v.chunks, v.slabs), v
+        assert v.reduce == (1 if v.slabs > limit else 0), v
+        if v.max_chunk:
+            assert v.chunks > 1 and any(d0 // c.n_sph != (d0 + n - 1) // c.n_sph for _, d0, n, _, _ in chunks), v
+        routes.setdefault((v.n, v.prec), set()).add((v.chunks > 1, v.reduce))
+    assert set(routes) == set(BC.VARIANT_SIZES)
+    for key, r in routes.items():
+        assert r == {(True, 1), (False, 0)}, key
+    for n, prec in BC.VARIANT_SIZES:
+        c = BC.cube(n, prec)
+        sh = BC.shards(c.n_gl * c.n_sph)
+        assert len(sh) == 3 and sh[0][0] == 0 and sh[-1][1] == c.n_gl * c.n_sph
+        assert all(a[1] == b[0] for a, b in zip(sh, sh[1:])) and len({b - a for a, b in sh}) == 3, sh
 
 
 # ---- the C-ABI without a GPU ------------------------------------------------------------------------------------
