@@ -547,7 +547,8 @@ struct GainLineParams {      // KB
     const cx<T>* a2;
     const cx<T>* tw;
     size_t a_bstride;        // batch stride (grid points) of a1 / a2
-    cx<T>* pout;             // out: P' [slot][x][y][z] -- a1 itself (in place) unless ab_interleaved
+    cx<T>* pout;             // out: P' [slot][x][y][z] -- a1 itself (in place) unless ab_interleaved.  The pipeline no longer
+                             // launches this kernel (see body_gain_line)
     size_t p_bstride;        // batch stride (elements) of pout
 };
 
@@ -597,6 +598,11 @@ struct GainLineAccParams {   // KB', exact-reduction mode: sum over the directio
     size_t a_bstride;        // batch strides (elements) of a1 / a2 and of pseg
     size_t pseg_bstride;
 };
+
+// KB of the faithful mode: every direction's own forward x transform, then the segment sum  sum_d dirw[d] * P'_d  in
+// registers.  Launched under the kind of KB' (same grid, threads and LDS); the parameter type selects the body.
+template <typename T>
+struct GainLineSumParams : GainLineAccParams<T> {};   // pseg: [segment][x][y][z], the segment sum of P'
 
 // Hermitian mode (f real): only the planes lx = 0 .. N/2 of A1', A2' are computed and stored.  For idx > N/2
 //   A'[idx](y,z) = conj(A'[N - idx](y,z)) + (-1)^y R1[idx](z) + (-1)^z R2[idx](y),
@@ -783,6 +789,28 @@ template <int N, typename T> constexpr bool ab_interleaved() {
 #else
     return sizeof(T) == 4 && N == 128 && pipelined_pair<N, T>();
 #endif
+}
+
+// Faithful mode: the x-line kernel loops over the directions of a segment and forms the segment sum of P' in registers
+// (body_gain_line_acc on GainLineSumParams) instead of writing every P'_d for KC to read back.  false: the geometry keeps
+// body_gain_line + one KC per chunk.  Left there: N = 128 in double precision (the loop body spills: 256 VGPRs + 16 B of
+// scratch per lane) and N = 80 / 96 (one workgroup per CU; N = 96 fp64 needs 350 VGPRs + 94 AGPRs), the geometries where
+// a looping kernel may stream worse than the one-shot one -- no same-box A/B of them exists yet, so they
+// run what they ran before.  BFSM_NO_SEGMENT_SUM restores that route everywhere, BFSM_SEGMENT_SUM_ALL takes the new one
+// everywhere (A/B builds).
+template <int N, typename T> constexpr bool kb_sums_segments() {
+#ifdef BFSM_NO_SEGMENT_SUM
+    return false;
+#elif defined(BFSM_SEGMENT_SUM_ALL)
+    return true;
+#else
+    return !(N == 80 || N == 96 || (N == 128 && sizeof(T) == 8));
+#endif
+}
+template <typename T> constexpr bool kb_sums_segments_n(int n) {
+    return n == 16 ? kb_sums_segments<16, T>() : n == 24 ? kb_sums_segments<24, T>() : n == 32 ? kb_sums_segments<32, T>()
+         : n == 40 ? kb_sums_segments<40, T>() : n == 48 ? kb_sums_segments<48, T>() : n == 64 ? kb_sums_segments<64, T>()
+         : n == 80 ? kb_sums_segments<80, T>() : n == 96 ? kb_sums_segments<96, T>() : n == 128 ? kb_sums_segments<128, T>() : false;
 }
 
 // A/B build (tools: -DBFSM_KA_XLANE): the LAST line pass of each KA tile at N = 128 fp32 as a wave-private pass.  The
@@ -1399,6 +1427,66 @@ BFSM_HD void body_gain_line_acc(const GainLineAccParams<T>& prm, Ctx& ctx) {
     const size_t obase = (size_t)ctx.bz() * prm.pseg_bstride + (size_t)(prm.seg0 + ctx.by()) * N * N * N + row;
 #pragma unroll
     for (int m = 0; m < E; ++m) ctx.template st_at<UNI>(prm.pseg + obase + (size_t)(u + TT * m) * N * N, pl, acc[m]);
+}
+
+// KB of the faithful mode with the segment sum of KC fused in.  grid = (column blocks, segments of the chunk, batch): the
+// frame of KB' above, the arithmetic of body_gain_line per direction -- both inverse x transforms, the product and the
+// direction's OWN forward x transform -- then  acc += dirw_d * P'_d  in direction order from zero, the sum KC formed from
+// the P'_d it read back.  The sum is pointwise in [x][y][z], so the workgroup that owns a column block for the whole
+// segment forms it and P' never reaches memory: 2 array reads per direction and 1 write per segment instead of 2 reads + 1
+// write (here) + 1 read (KC) per direction.  KC then transforms pseg once per segment (weights 1).
+// Barriers: the exchange of the forward transform is left open behind its reads, the next direction's first exchange
+// has the barrier in front of its writes -- three exchanges and six barriers per direction as in body_gain_line, and the
+// loads of the next direction issue without a rendezvous.
+template <int N, typename T, class Ctx>
+BFSM_HD void body_gain_line_acc(const GainLineSumParams<T>& prm, Ctx& ctx) {
+    constexpr int E = Wg<N>::E, TT = Wg<N>::T;
+    constexpr int NPL = Wg<N>::NPL;
+    int p, u;                                   // p: column inside this block of NPL
+    lane_coords<NPL, Wg<N>::LROW>(ctx, p, u);
+    cx<T>* lds = ctx.template lds<cx<T>>();
+    Twiddles<N, T> twr;
+    twr.load(prm.tw, u, ctx);
+    const Segment seg = prm.segs[prm.seg0 + ctx.by()];
+    const size_t row = (size_t)ctx.bx() * NPL;                   // uniform; the lane adds pl bytes
+    const unsigned pl = (unsigned)p * (unsigned)sizeof(cx<T>);
+    constexpr bool UNI = Wg<N>::LROW % 64 == 0;
+    cx<T> acc[E];
+#pragma unroll
+    for (int m = 0; m < E; ++m) acc[m] = {(T)0, (T)0};
+    for (int d = seg.d0; d < seg.d0 + seg.n; ++d) {
+        const size_t base = (size_t)ctx.bz() * prm.a_bstride + (size_t)d * N * N * N + row;
+        cx<T> a[E], b[E];
+        if constexpr (ab_interleaved<N, T>()) {
+#pragma unroll
+            for (int m = 0; m < E; ++m)
+                ctx.template ld_stream_pair_at<UNI>(prm.a1 + 2 * (base + (size_t)(u + TT * m) * N * N), 2 * pl, a[m], b[m]);
+        } else {
+#pragma unroll
+            for (int m = 0; m < E; ++m) a[m] = ctx.template ld_stream_at<UNI>(prm.a1 + base + (size_t)(u + TT * m) * N * N, pl);
+#pragma unroll
+            for (int m = 0; m < E; ++m) b[m] = ctx.template ld_stream_at<UNI>(prm.a2 + base + (size_t)(u + TT * m) * N * N, pl);
+        }
+        fft_line_np<N, NPL, +1, T, false, SYNC_PRE | SYNC_POST>(a, lds, p, u, twr, ctx);
+        fft_line_np<N, NPL, +1, T, false, SYNC_POST>(b, lds, p, u, twr, ctx);
+#pragma unroll
+        for (int m = 0; m < E; ++m) a[m] = cmul(a[m], b[m]);
+        fft_line_np<N, NPL, -1, T, false, 0>(a, lds, p, u, twr, ctx);
+        const T w = prm.dirw[prm.dir0 + d];
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            acc[m].x += w * a[m].x;
+            acc[m].y += w * a[m].y;
+        }
+    }
+    // One store burst per segment, a and b dead: per-lane addresses.  Compiler workaround: with st_at<UNI> here (the
+    // scalar-base form the loads use) every geometry with UNI fails to compile under AMD clang 22.0.0git (ROCm 7.2.0,
+    // -O3 --offload-arch=gfx950): "error: illegal VGPR to SGPR copy", once per store, from the "+s" constraint on the
+    // row pointer directly behind the direction loop (KB' has a transform and its barrier in between and compiles).
+    // To see whether a newer compiler accepts it, replace <false> by <UNI> and build; nothing else depends on it.
+    const size_t obase = (size_t)ctx.bz() * prm.pseg_bstride + (size_t)(prm.seg0 + ctx.by()) * N * N * N + row;
+#pragma unroll
+    for (int m = 0; m < E; ++m) ctx.template st_at<false>(prm.pseg + obase + (size_t)(u + TT * m) * N * N, pl, acc[m]);
 }
 
 // KN (Hermitian mode).  grid = (column blocks, 2 * directions of the chunk, batch).  One column = one (kind, j):

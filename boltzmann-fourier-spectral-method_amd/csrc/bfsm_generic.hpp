@@ -2,8 +2,8 @@
 // are 2, 3, 5, 7, 11, 13 (non-cubic boxes, N = 20, 112, 160, ...), which the reference plans with cufftPlan3d / cufftPlanMany
 // (Collisions/CUDABoltzmannOperator.cu:86-100) and fftw_plan_dft_3d (Collisions/FFTWBoltzmannOperator.cpp:64-65).
 //
-// The cubic grids N in {16, 24, 32, 40, 48, 64, 80, 96, 128} run on the fused three-kernel pipeline of bfsm_core.hpp (6 array passes
-// per direction); everything else runs here, on mixed-radix (8, 4, 2, 3, 5; 7, 11, 13 table-driven) Stockham passes in LDS
+// The cubic grids N in {16, 24, 32, 40, 48, 64, 80, 96, 128} run on the fused three-kernel pipeline of bfsm_core.hpp (4 array passes
+// per direction: its x-line kernel sums the directions of a segment in registers); everything else runs here, on mixed-radix (8, 4, 2, 3, 5; 7, 11, 13 table-driven) Stockham passes in LDS
 // with runtime sizes.  Three sequences, chosen per box in GenericPipeline (profiles/r04_generic_fused_ab.txt):
 //   * the (y,z) plane fits the LDS (most boxes up to ~1300 plane points in double precision): the cubic pipeline's three
 //     kernels in size-generic form -- body_gen_plane_pair / body_gen_plane straight from f_hat with the phase multiply on the

@@ -300,7 +300,8 @@ struct Pipeline {
     cx<T>* qhat = nullptr;
     cx<T>* a1 = nullptr;
     cx<T>* a2 = nullptr;
-    cx<T>* pp = nullptr;          // P': a1 itself (KB works in place) unless the scratch is interleaved (own buffer)
+    cx<T>* pp = nullptr;          // P' (per-direction route of the faithful mode only): a1 itself (KB works in place)
+                                  // unless the scratch is interleaved (own buffer)
     cx<T>* slab = nullptr;
     cx<T>* tw = nullptr;
     cx<T>* phx = nullptr;
@@ -310,7 +311,7 @@ struct Pipeline {
     T* beta1 = nullptr;
     T* beta2 = nullptr;
     Segment* segs = nullptr;
-    // exact-reduction mode only
+    // segment sums formed by the x-line kernel (every mode but the per-direction route of the faithful mode)
     cx<T>* pseg = nullptr;        // [segment][x][y][z]
     Segment* segs_unit = nullptr; // one single-slot segment per pseg entry, same r
     T* ones = nullptr;
@@ -332,6 +333,9 @@ struct Pipeline {
     // A1' / A2' interleaved per element in one array (bfsm_core.hpp, ab_interleaved)
     bool pair_geometry() const { return plan.N == 128 && ab_interleaved<128, T>(); }
     bool interleaved() const { return pair_geometry() && !plan.hermitian; }
+    // the x-line kernel forms the segment sums (pseg) and ONE KC pass over them follows all chunks; false: the faithful
+    // mode's per-direction route (KB writes every P'_d, one KC per chunk reads them back)
+    bool segment_sums() const { return plan.exact_reductions || kb_sums_segments_n<T>(plan.N); }
     int a_planes = 0;        // lx planes of A1' / A2' kept per direction (N, or N/2 + 1 in the Hermitian mode)
     size_t r_per_dir() const { return (size_t)4 * (plan.N / 2 - 1) * plan.N; }
     int max_batch = 1;       // distributions evaluated per call; scratch scales with it
@@ -356,9 +360,9 @@ struct Pipeline {
         a_planes = plan.hermitian ? plan.N / 2 + 1 : plan.N;
         const size_t Gp = (size_t)a_planes * plan.N * plan.N;       // elements of A1' / A2' per direction
         if (interleaved()) {
-            // {A1', A2'} side by side in a1; the faithful mode's KB writes P' to a buffer of its own (see ab_interleaved)
+            // {A1', A2'} side by side in a1; a KB that writes every P'_d needs a buffer of its own for it (see ab_interleaved)
             ok = ok && (a1 = (cx<T>*)be->alloc(2 * nb * cap * Gp * sizeof(cx<T>)));
-            if (!plan.exact_reductions) ok = ok && (pp = (cx<T>*)be->alloc(nb * cap * G * sizeof(cx<T>)));
+            if (!segment_sums()) ok = ok && (pp = (cx<T>*)be->alloc(nb * cap * G * sizeof(cx<T>)));
         } else {
             ok = ok && (a1 = (cx<T>*)be->alloc(nb * cap * Gp * sizeof(cx<T>)));
             ok = ok && (a2 = (cx<T>*)be->alloc(nb * cap * Gp * sizeof(cx<T>)));
@@ -368,7 +372,7 @@ struct Pipeline {
         ok = ok && (slab = (cx<T>*)be->alloc(nb * nslab * G * sizeof(cx<T>)));
         ok = ok && dev_copy(tw, t.tw) && dev_copy(phx, t.phx) && dev_copy(phy, t.phy) && dev_copy(phz, t.phz);
         ok = ok && dev_copy(dirw, t.dirw) && dev_copy(beta1, t.beta1) && dev_copy(beta2, t.beta2) && dev_copy(segs, plan.segs);
-        if (ok && plan.exact_reductions) {
+        if (ok && segment_sums()) {
             std::vector<Segment> unit(plan.segs.size());
             for (size_t i = 0; i < unit.size(); ++i) unit[i] = Segment{(int)i, 1, plan.segs[i].r, 0};
             std::vector<T> one(unit.size() ? unit.size() : 1, (T)1);
@@ -510,7 +514,12 @@ struct Pipeline {
                 be->template launch<K::GainInvNyq, T>(a_planes, ga + kn_rows, nb, kan, N);
             } else if (pair_geometry() && !interleaved()) be->template launch<K::GainInvTwo, T>(a_planes, ga, nb, ka, N);
             else be->template launch<K::GainInv, T>(a_planes, ga, nb, ka, N);
-            if (!plan.exact_reductions) {
+            if (!plan.exact_reductions && segment_sums()) {
+                // faithful mode: every direction's own forward x transform, the segment sum of P' in registers
+                GainLineSumParams<T> kb{{a1, a2, pseg, dirw, segs, tw, c.dir0, c.seg0, a_bs, s_bs}};
+                be->mark(BFSM_K_GAIN_LINE, (2.0 * c.n + c.n_seg) * Gc);
+                be->template launch<K::GainLineAcc, T>(line_blocks(), c.n_seg, nb, kb, N);
+            } else if (!plan.exact_reductions) {
                 const size_t p_bs = interleaved() ? cap * G : a_bs;
                 GainLineParams<T> kb{a1, a2, tw, a_bs, pp, p_bs};
                 be->mark(BFSM_K_GAIN_LINE, 3.0 * c.n * Gc);
@@ -534,7 +543,7 @@ struct Pipeline {
                 be->template launch<K::GainLineAccH, T>(line_blocks(), c.n_seg, nb, kb, N);
             }
         }
-        if (plan.exact_reductions && slab_count) {   // one forward tile pass per segment, all chunks at once
+        if (segment_sums() && slab_count) {   // one forward tile pass per segment, all chunks at once
             GainFwdParams<T> kc{pseg, slab, ones, segs_unit, tw, 0, 0, s_bs, s_bs};
             be->mark(BFSM_K_GAIN_FWD, 1.0 * (double)slab_count * Gc);
             be->template launch<K::GainFwd, T>(N, (int)slab_count, nb, kc, N);
@@ -590,14 +599,19 @@ inline double alg_bytes_per_eval(const PlanInfo& p) {
     return (6.0 * (double)(p.full_end - p.full_begin) + 9.0) * (double)p.G() * c;
 }
 
-// Bytes the launch sequence actually moves (model): equals the figure above in the faithful mode (+ slabs); in the
-// exact-reduction mode 4 array passes per effective direction + 2 per segment.
+// Bytes the launch sequence actually moves (model).  Faithful mode: 4 array passes per direction (KA writes A1', A2', the
+// x-line kernel reads them) + 4 per segment (segment sum written and read, slab written and read); 6 per direction + 2 per
+// segment on the per-direction route (P'_d written and read back).  Exact-reduction mode: the same 4 + 4 per EFFECTIVE
+// direction and segment.
 inline double moved_bytes_per_eval(const PlanInfo& p) {
     const double c = p.precision == BFSM_F64 ? 16.0 : 8.0;
     const double G = (double)p.G(), n = (double)p.n_dirs(), sg = (double)p.segs.size();
     // size-generic path: one pass per axis (or x + a fused (y,z) plane pass), pointwise steps fused on the load side
     if (p.N == 0) return ((double)p.gen_moves * n + 2.0 * p.gen_slabs + (p.gen_plane ? 18.0 : 27.0)) * G * c;
-    if (!p.exact_reductions) return (6.0 * n + 2.0 * sg + 9.0) * G * c;
+    if (!p.exact_reductions) {
+        const bool sums = p.precision == BFSM_F64 ? kb_sums_segments_n<double>(p.N) : kb_sums_segments_n<float>(p.N);
+        return sums ? (4.0 * n + 4.0 * sg + 9.0) * G * c : (6.0 * n + 2.0 * sg + 9.0) * G * c;
+    }
     const double h = p.hermitian ? (double)(p.N / 2 + 1) / p.N : 1.0;
     return (4.0 * n * h + 4.0 * sg + 9.0) * G * c;
 }

@@ -62,9 +62,9 @@ enum {
      *       forward-transformed once, instead of one forward FFT per direction.
      * The default (flag clear) evaluates every direction: its own two inverse 3-D transforms, its own product and the
      * x part of its own forward transform; the (y,z) part of the forward transform is applied once to the weighted sum
-     * of a run of directions that share a radial node (linearity; every array is still written and read once per
-     * direction: 6 array passes per direction).  Build with -DBFSM_KC_PER_DIRECTION for one (y,z)
-     * forward transform per direction (the reference's literal loop, FFTWBoltzmannOperator.cpp:249).
+     * of a run of directions that share a radial node (linearity).  That sum is formed in registers by the kernel that
+     * runs the x transforms, so the half-transformed product of a direction is never written: A1' and A2' are written
+     * and read once per direction, the sum once per run -- 4 array passes per direction + 4 per run, DESIGN.md section 4.
      * On boxes served by the size-generic path (see bfsm_desc::nvx) this flag and BFSM_FLAG_HERMITIAN are accepted and
      * have no effect (the results are the same by definition; bfsm_counters::exact_reductions reports 0). */
     BFSM_FLAG_EXACT_REDUCTIONS = 2,
@@ -104,7 +104,7 @@ typedef struct bfsm_plan* bfsm_handle;
 typedef struct bfsm_desc {
     int nvx, nvy, nvz;        /* velocity grid: every extent even, in [4, 256], prime factors 2, 3, 5, 7, 11, 13 (the
                                  reference plans any Nvx x Nvy x Nvz, CUDABoltzmannOperator.cu:86-100).  Cubes of 16, 24, 32,
-                                 40, 48, 64, 80, 96, 128 run on the fused pipeline (6 array passes per direction); every other box
+                                 40, 48, 64, 80, 96, 128 run on the fused pipeline (4 array passes per direction); every other box
                                  on the size-generic path (run-time sizes: the same three fused kernels where a (y,z) plane
                                  fits the LDS, per-axis passes otherwise; a half to a sixth of the fused pipeline's speed),
                                  both precisions.  Anything else: BFSM_ERR_UNSUPPORTED */
@@ -140,8 +140,9 @@ typedef struct bfsm_counters {
     int n_chunks;
     int chunk_dirs;                       /* directions in the largest chunk                               */
     long long n_dirs;                     /* work units of this shard (directions; antipodal pairs if merged) */
-    double moved_bytes_per_eval;          /* bytes the launch sequence moves (model); == alg bytes + slabs unless
-                                             BFSM_FLAG_EXACT_REDUCTIONS is set                                */
+    double moved_bytes_per_eval;          /* bytes the launch sequence moves (model): (4*n_dirs + 4*segments + 9) * G * c
+                                             on the fused pipeline (n_dirs: work units of the mode), i.e. LESS than
+                                             alg_bytes_per_eval, the reference model of three transforms per direction */
     int exact_reductions;                 /* 1 if the flag is active                                          */
     int antipodal_merged;                 /* 1 if antipodal pairs were merged                                 */
 } bfsm_counters;

@@ -1,4 +1,5 @@
-// Streaming ceiling of KB's access pattern (two arrays read, one written in place; x-lines of N points at stride N*N, NPL
+// Streaming ceiling of the access pattern KB had until it summed the segments in registers (it no longer
+// writes P'): two arrays read, one written in place; x-lines of N points at stride N*N, NPL
 // contiguous columns per workgroup), no LDS, no butterflies: what does the memory system give this pattern?
 //   case A: N = 128, fp32 complex (8 B), NPL = 64 columns  -> 512-byte runs   (config 5's KB)
 //   case B: N = 128, fp32 complex, NPL = 128 columns        -> 1-KiB runs
