@@ -20,6 +20,8 @@ EXPORTED_SYMBOLS = (
     "bfsm_synchronize", "bfsm_fft3d", "bfsm_get_counters", "bfsm_destroy", "bfsm_last_error", "bfsm_backend_name",
     "bfsm_version", "bfsm_collide_bilinear", "bfsm_collide_bilinear_async", "bfsm_collide_bilinear_partial_async",
     "bfsm_conserve_async",
+    "bfsm_collide_split", "bfsm_collide_split_async", "bfsm_collide_split_batch_partial_async",
+    "bfsm_collide_bilinear_split_partial_async", "bfsm_loss_rate_async",
 )
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -105,6 +107,16 @@ def load_library(path=None):
     L.bfsm_collide_bilinear_partial_async.restype = ctypes.c_int
     L.bfsm_conserve_async.argtypes = [vp, vp, ctypes.c_int, vp]
     L.bfsm_conserve_async.restype = ctypes.c_int
+    # the gain / loss split: typed where the library has it (the presence of the symbols is the capability check, so that an
+    # older build named by BFSM_LIB still loads)
+    for name, args in (("bfsm_collide_split", [vp, vp, vp, vp]), ("bfsm_collide_split_async", [vp, vp, vp, vp, vp]),
+                       ("bfsm_collide_split_batch_partial_async", [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp]),
+                       ("bfsm_collide_bilinear_split_partial_async", [vp, vp, vp, vp, vp, ctypes.c_int, vp]),
+                       ("bfsm_loss_rate_async", [vp, vp, vp, ctypes.c_int, vp])):
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = ctypes.c_int
     L.bfsm_qhat_buffer.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int)]
     L.bfsm_qhat_buffer.restype = vp
     L.bfsm_synchronize.argtypes = [vp]

@@ -176,6 +176,60 @@ class HIPBoltzmannOperator:
         self.computeBilinearCollision(tmp, h, f)
         Q.add_(tmp.view(Q.shape))
 
+    # Gain / loss split (include/bfsm.h, bfsm_collide_split*): Qgain = the gain Q+, nu = the collision frequency nu[f], so that
+    # Q = Qgain - f * nu (bilinear form: Qgain - g * nu).  BFSM_FLAG_CONSERVE has no effect on them.
+    def _require_batch(self, n_batch, *tensors):
+        if self._h is None:
+            raise RuntimeError("initialize() has not been called")
+        G = self.Nvx * self.Nvy * self.Nvz
+        for t in tensors:
+            if t is None:
+                continue
+            if not (t.is_cuda and t.dtype.is_floating_point and t.element_size() == 8 and t.is_contiguous()
+                    and t.numel() == int(n_batch) * G):
+                raise ValueError("arguments must be contiguous float64 CUDA tensors with n_batch*Nvx*Nvy*Nvz elements")
+
+    def computeCollisionSplit(self, Qgain, nu, f_in):
+        """Blocking Qgain = Q+(f,f), nu = nu[f], device tensors; needs a handle that owns all directions."""
+        self._require_batch(1, Qgain, nu, f_in)
+        self._check(self._lib.bfsm_collide_split(self._h, _ptr(Qgain), _ptr(nu), _ptr(f_in)))
+
+    def computeCollisionSplitAsync(self, Qgain, nu, f_in, stream=0):
+        self._require_batch(1, Qgain, nu, f_in)
+        self._check(self._lib.bfsm_collide_split_async(self._h, _ptr(Qgain), _ptr(nu), _ptr(f_in), ctypes.c_void_p(stream)))
+
+    def collideSplitBatchPartial(self, Qgain, nu, f_in, n_batch, with_loss, stream=0):
+        """Batch x direction shard: member i of Qgain = this shard's part of the gain of member i (the caller sums it over the
+        ranks); nu (written only if with_loss, otherwise it may be None) = nu[f_i]."""
+        self._require_batch(n_batch, Qgain, nu, f_in)
+        if with_loss and nu is None:
+            raise ValueError("nu may be None only with with_loss = False")
+        self._check(self._lib.bfsm_collide_split_batch_partial_async(
+            self._h, _ptr(Qgain), _ptr(nu) if nu is not None else None, _ptr(f_in), int(n_batch), 1 if with_loss else 0,
+            ctypes.c_void_p(stream)))
+
+    def collideBilinearSplitPartial(self, Qgain, nu, g, f, with_loss, stream=0):
+        """This shard's part of the gain of Q(g, f) and, if with_loss, nu = nu[f] (else nu may be None)."""
+        self._require_batch(1, Qgain, nu, g, f)
+        if with_loss and nu is None:
+            raise ValueError("nu may be None only with with_loss = False")
+        self._check(self._lib.bfsm_collide_bilinear_split_partial_async(
+            self._h, _ptr(Qgain), _ptr(nu) if nu is not None else None, _ptr(g), _ptr(f), 1 if with_loss else 0,
+            ctypes.c_void_p(stream)))
+
+    def computeBilinearSplit(self, Qgain, nu, g, f):
+        """Blocking Qgain = Q+(g, f), nu = nu[f]: Q(g, f) = Qgain - g * nu; needs a handle that owns all directions."""
+        n_dirs = self.gl_quadrature.getNumberOfPoints() * self.spherical_quadrature.getNumberOfPoints()
+        if self._dir_range not in ((0, 0), (0, n_dirs)):
+            raise ValueError("computeBilinearSplit needs a handle that owns all directions; use collideBilinearSplitPartial")
+        self.collideBilinearSplitPartial(Qgain, nu, g, f, True)
+        self.synchronize()
+
+    def lossRate(self, nu, f_in, n_batch=1, stream=0):
+        """nu = nu[f] = Re IFFT(beta2 f_hat / G) for n_batch distributions, no gain work; any handle; enqueued on `stream`."""
+        self._require_batch(n_batch, nu, f_in)
+        self._check(self._lib.bfsm_loss_rate_async(self._h, _ptr(nu), _ptr(f_in), int(n_batch), ctypes.c_void_p(stream)))
+
     def gainPartial(self, f_in, stream=0):
         self._require(f_in)
         self._check(self._lib.bfsm_gain_partial(self._h, _ptr(f_in), ctypes.c_void_p(stream)))

@@ -665,6 +665,22 @@ struct TailLineParams {      // tail step 2: x inverse of both, Q = Re(gain) - R
     int with_loss;           // 0: Q = Re(gain) only (partial result of a rank that does not own the loss term)
 };
 
+// Gain / loss split (include/bfsm.h, bfsm_collide_split*): the tail kernels selected by parameter type, launched under
+// K::TailInv / K::TailLine, so that the instantiations of the combined Q are the code they were.
+// Tail step 1 of bfsm_loss_rate_async: the loss plane only (grid.y = 1), no gain work
+template <typename T>
+struct TailInvLossParams : TailInvParams<T> {};
+template <class P> struct tail_loss_only { static constexpr bool value = false; };
+template <typename T> struct tail_loss_only<TailInvLossParams<T>> { static constexpr bool value = true; };
+// Tail step 2 with the two terms kept apart: Q = Re(gain) (the gain Q+), nu = Re(loss) (the collision frequency); f is
+// not read.  The pipeline launches it only with the loss term (without, the combined form already stores Re(gain) alone)
+template <typename T>
+struct TailLineSplitParams : TailLineParams<T> {
+    double* nu;
+};
+template <class P> struct tail_split { static constexpr bool value = false; };
+template <typename T> struct tail_split<TailLineSplitParams<T>> { static constexpr bool value = true; };
+
 BFSM_HD int mode_of(int i, int n) { return i < n / 2 ? i : i - n; }
 
 // XCD-aware block index.  Workgroups are handed to the 8 XCDs round-robin by their linear id, and every XCD has its own
@@ -1864,13 +1880,14 @@ BFSM_HD void body_reduce(const ReduceParams<T>& prm, Ctx& ctx) {
 // Tail 1.  grid = (N planes lx, 2).  y==0: Q_hat plane; y==1: beta2 * f_hat / G
 // (compute_beta2_times_f_hat, BoltzmannCUDAKernels.cu:126-159, with beta2 tabulated by |l|^2), then the
 // (lz,ly) -> (y,z) part of the two single inverse transforms (CUDABoltzmannOperator.cu:203-212).
-template <int N, typename T, class Ctx>
-BFSM_HD void body_tail_inv(const TailInvParams<T>& prm, Ctx& ctx) {
+// P = TailInvLossParams: every workgroup forms a loss plane (grid.y = 1).
+template <int N, typename T, class Ctx, class P>
+BFSM_HD void body_tail_inv(const P& prm, Ctx& ctx) {
     constexpr int E = Wg<N>::E, TT = Wg<N>::T;
     int p, u;
     lane_coords<N, Wg<N>::ROW>(ctx, p, u);
     const int lxi = ctx.bx();
-    const bool loss = ctx.by() != 0;
+    const bool loss = tail_loss_only<P>::value || ctx.by() != 0;
     cx<T>* lds = ctx.template lds<cx<T>>();
     Twiddles<N, T> twr;
     twr.load(prm.tw, u, ctx);
@@ -1919,8 +1936,9 @@ BFSM_HD void body_tail_inv(const TailInvParams<T>& prm, Ctx& ctx) {
 
 // Tail 2.  grid.x = N rows y.  x-part of both inverse transforms + compute_Q_total
 // (BoltzmannCUDAKernels.cu:162-177): Q = Re(Q_gain) - Re(beta2_times_f * f), f real.
-template <int N, typename T, class Ctx>
-BFSM_HD void body_tail_line(const TailLineParams<T>& prm, Ctx& ctx) {
+// P = TailLineSplitParams: Q = Re(gain), nu = Re(loss), two stores and no load of f.
+template <int N, typename T, class Ctx, class P>
+BFSM_HD void body_tail_line(const P& prm, Ctx& ctx) {
     constexpr int E = Wg<N>::E, TT = Wg<N>::T;
     constexpr int NPL = Wg<N>::NPL;
     int p, u;                                   // p: column inside this block of NPL
@@ -1933,7 +1951,17 @@ BFSM_HD void body_tail_line(const TailLineParams<T>& prm, Ctx& ctx) {
 #pragma unroll
     for (int m = 0; m < E; ++m) g[m] = prm.tg[base + (size_t)(u + TT * m) * N * N];
     fft_line_np<N, NPL, +1, T>(g, lds, p, u, twr, ctx);
-    if (prm.with_loss) {
+    if constexpr (tail_split<P>::value) {
+#pragma unroll
+        for (int m = 0; m < E; ++m) l[m] = prm.tl[base + (size_t)(u + TT * m) * N * N];
+        fft_line_np<N, NPL, +1, T>(l, lds, p, u, twr, ctx);
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            const size_t i = base + (size_t)(u + TT * m) * N * N;
+            prm.Q[i] = (double)g[m].x;
+            prm.nu[i] = (double)l[m].x;
+        }
+    } else if (prm.with_loss) {
 #pragma unroll
         for (int m = 0; m < E; ++m) l[m] = prm.tl[base + (size_t)(u + TT * m) * N * N];
         fft_line_np<N, NPL, +1, T>(l, lds, p, u, twr, ctx);

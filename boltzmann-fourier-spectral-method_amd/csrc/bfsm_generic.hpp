@@ -848,13 +848,27 @@ BFSM_HD void body_gen_acc(const GenAccParams<T>& prm, Ctx& ctx) {
     qh[idx] = q;
 }
 
-template <typename T, class Ctx>
-BFSM_HD void body_gen_combine(const GenCombineParams<T>& prm, Ctx& ctx) {
+// Gain / loss split (include/bfsm.h, bfsm_collide_split*): Q = Re(gain), nu = Re(loss), f not read.  A parameter type of
+// its own, launched under GK::Combine and only with the loss term, so that the combined instantiation is the code it was.
+template <typename T>
+struct GenCombineSplitParams : GenCombineParams<T> {
+    double* nu;
+};
+template <class P> struct gen_split { static constexpr bool value = false; };
+template <typename T> struct gen_split<GenCombineSplitParams<T>> { static constexpr bool value = true; };
+
+template <typename T, class Ctx, class P>
+BFSM_HD void body_gen_combine(const P& prm, Ctx& ctx) {
     const size_t idx = (size_t)ctx.bx() * ctx.nthreads() + ctx.tid();
     if (idx >= prm.G) return;
-    double q = (double)prm.g[idx].x;
-    if (prm.with_loss) q -= (double)prm.l[idx].x * prm.f[idx];
-    prm.Q[idx] = q;
+    if constexpr (gen_split<P>::value) {
+        prm.Q[idx] = (double)prm.g[idx].x;
+        prm.nu[idx] = (double)prm.l[idx].x;
+    } else {
+        double q = (double)prm.g[idx].x;
+        if (prm.with_loss) q -= (double)prm.l[idx].x * prm.f[idx];
+        prm.Q[idx] = q;
+    }
 }
 
 enum class GK { Fft, Acc, Combine, FftBig, Plane, Line3, PlaneAcc, PlanePair, Fft8, FftBig8, Line38 };   // ...8: 8 lines per workgroup   // FftBig: Fft + the radix-7 / 11 / 13 passes; Plane: y and z
@@ -1245,12 +1259,12 @@ struct GenericPipeline {
 
     // Bilinear form Q(g,f): as Pipeline::collide_bilinear (g_hat in fhat, f_hat in fhat + G: init reserves two spectra)
     cx<T>* fhat_b() const { return fhat + G; }
-    void collide_bilinear(double* Q_dev, const double* g_dev, const double* f_dev, bool with_loss) {
+    void collide_bilinear(double* Q_dev, const double* g_dev, const double* f_dev, bool with_loss, double* nu_dev = nullptr) {
         spectrum(g_dev, fhat, 1);
         const cx<T>* fb = fhat;
         if (f_dev != g_dev) { spectrum(f_dev, fhat_b(), 1); fb = fhat_b(); }
         gain_spectra(1, fb);
-        finish(Q_dev, g_dev, with_loss, 1, false, fb);
+        finish(Q_dev, g_dev, with_loss, 1, false, fb, nu_dev);
     }
 
     // the gain term of this shard from fhat (and fb: the conj(alpha) operand of the bilinear form) into qhat
@@ -1317,7 +1331,9 @@ struct GenericPipeline {
 
     // loss term + final inverse transforms + combine   (CUDABoltzmannOperator.cu:193-216)
     // loss_hat (bilinear form): the spectrum the loss term convolves (f_hat); f_dev is then g, which multiplies it
-    void finish(double* Q_dev, const double* f_dev, bool with_loss = true, int nb = 1, bool = false, const cx<T>* loss_hat = nullptr) {
+    // nu_dev (gain / loss split): Q_dev = Re IFFT(qhat) and, with_loss, nu_dev = Re IFFT(beta2 f_hat / G); f_dev is not read
+    void finish(double* Q_dev, const double* f_dev, bool with_loss = true, int nb = 1, bool = false, const cx<T>* loss_hat = nullptr,
+                double* nu_dev = nullptr) {
         const double Gc = (double)G * sizeof(cx<T>);
         cx<T>* tg = tail;                                   // [max_batch][G] gain, then [max_batch][G] loss
         cx<T>* tl = tail + (size_t)max_batch * G;
@@ -1345,6 +1361,31 @@ struct GenericPipeline {
         }
         const size_t tot = (size_t)nb * G;                  // members are contiguous in every array involved
         GenCombineParams<T> kc{tg, tl, f_dev, Q_dev, tot, with_loss ? 1 : 0};
+        be->mark(BFSM_K_TAIL, 0);
+        if (nu_dev && with_loss) {
+            GenCombineSplitParams<T> ks{};
+            static_cast<GenCombineParams<T>&>(ks) = kc;
+            ks.f = nullptr;
+            ks.nu = nu_dev;
+            be->template launch_gen<GK::Combine, T>((int)((tot + GEN_THREADS - 1) / GEN_THREADS), 1, GEN_THREADS, 0, ks);
+        } else be->template launch_gen<GK::Combine, T>((int)((tot + GEN_THREADS - 1) / GEN_THREADS), 1, GEN_THREADS, 0, kc);
+    }
+
+    // nu = Re IFFT(beta2 f_hat / G) alone (bfsm_loss_rate_async): FFT(f), the inverse transform of beta2 f_hat (the factor on
+    // the load side of its x pass), the real part.  nb > 1 only where batch_together(), as in gain_partial.
+    void loss_rate(double* nu_dev, const double* f_dev, int nb = 1) {
+        const double Gc = (double)G * sizeof(cx<T>);
+        spectrum(f_dev, fhat, nb);
+        cx<T>* tl = tail + (size_t)max_batch * G;
+        be->mark(BFSM_K_TAIL, 3.5 * nb * Gc);
+        pass(fhat, nullptr, tl, nb, 0, +1, GEN_BETA2, G, G);
+        if (plane_ok()) { be->mark(BFSM_K_TAIL, 0); plane(tl, nullptr, tl, nb, +1, GEN_PLAIN, G, G); }
+        else {
+            be->mark(BFSM_K_TAIL, 0); pass(tl, nullptr, tl, nb, 1, +1, GEN_PLAIN, G, G);
+            be->mark(BFSM_K_TAIL, 0); pass(tl, nullptr, tl, nb, 2, +1, GEN_PLAIN, G, G);
+        }
+        const size_t tot = (size_t)nb * G;
+        GenCombineParams<T> kc{tl, tl, nullptr, nu_dev, tot, 0};
         be->mark(BFSM_K_TAIL, 0);
         be->template launch_gen<GK::Combine, T>((int)((tot + GEN_THREADS - 1) / GEN_THREADS), 1, GEN_THREADS, 0, kc);
     }

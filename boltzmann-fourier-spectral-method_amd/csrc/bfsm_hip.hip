@@ -600,6 +600,15 @@ static int check_hip(bfsm_plan* h, const char* where) {
     return fail(h, BFSM_ERR_HIP, m);
 }
 
+// a batch through `fn(pipeline, first member, members)`: together where the pipeline's launches cover a batch, else one by one
+template <class F>
+static void for_batch(bfsm_plan* h, int n_batch, F&& fn) {
+    bool together = true;
+    if (h->g64 || h->g32) h->with([&](auto& p) { together = p.batch_together(); });
+    if (together) h->with([&](auto& p) { fn(p, 0, n_batch); });
+    else for (int i = 0; i < n_batch; ++i) h->with([&](auto& p) { fn(p, i, 1); });
+}
+
 extern "C" {
 
 #ifdef BFSM_TOOLS_BUILD
@@ -881,6 +890,92 @@ int bfsm_collide_bilinear(bfsm_handle h, double* Q_dev, const double* g_dev, con
     int rc = bfsm_collide_bilinear_async(h, Q_dev, g_dev, f_dev, nullptr);
     if (rc) return rc;
     return bfsm_synchronize(h);
+}
+
+// Gain / loss split: the sequences of bfsm_collide_batch_partial_async / bfsm_collide_bilinear_partial_async with the two terms
+// of the tail kept apart (Pipeline::finish / GenericPipeline::finish with nu_dev).  N = 16 takes the plane-tile pipeline.  No
+// projection: BFSM_FLAG_CONSERVE applies to Q, not to its parts.
+static bool ranges_overlap(const double* a, const double* b, size_t n) { return a < b + n && b < a + n; }
+
+int bfsm_collide_split_batch_partial_async(bfsm_handle h, double* Qgain_dev, double* nu_dev, const double* f_dev, int n_batch,
+                                           int with_loss, void* stream) {
+    if (!h) return BFSM_ERR_INVALID;
+    BFSM_GUARDED(h,
+        DeviceGuard g(h->desc.device);
+        int rc = enter(h, g, stream);
+        if (rc) return rc;
+        if (!f_dev || !Qgain_dev) return fail(h, BFSM_ERR_INVALID, "null f or Qgain");
+        if (with_loss && !nu_dev) return fail(h, BFSM_ERR_INVALID, "null nu (it may be null only with with_loss = 0)");
+        int cap = 1;
+        h->with([&](auto& p) { cap = p.max_batch; });
+        if (n_batch < 1 || n_batch > cap)
+            return fail(h, BFSM_ERR_INVALID, "n_batch must be in [1, max_batch of the descriptor]");
+        const size_t n = (size_t)n_batch * h->G;
+        if (ranges_overlap(Qgain_dev, f_dev, n) || (nu_dev && (ranges_overlap(nu_dev, f_dev, n) || ranges_overlap(nu_dev, Qgain_dev, n))))
+            return fail(h, BFSM_ERR_INVALID, "Qgain and nu must not overlap each other or f");
+        h->be.begin_eval();
+        double* nu = with_loss ? nu_dev : nullptr;
+        for_batch(h, n_batch, [&](auto& p, int i0, int nb) {
+            const size_t o = (size_t)i0 * h->G;
+            const bool fu = p.fuse_reduce();
+            p.gain_partial(f_dev + o, nb, !fu);
+            p.finish(Qgain_dev + o, nullptr, with_loss != 0, nb, fu, nullptr, nu ? nu + o : nullptr);
+        });
+        return leave(h, "bfsm_collide_split");
+    )
+}
+
+int bfsm_collide_split_async(bfsm_handle h, double* Qgain_dev, double* nu_dev, const double* f_dev, void* stream) {
+    if (!h) return BFSM_ERR_INVALID;
+    if (!h->full_shard)
+        return fail(h, BFSM_ERR_INVALID, "bfsm_collide_split needs a handle that owns all directions; use bfsm_collide_split_batch_partial_async + a sum over the ranks");
+    return bfsm_collide_split_batch_partial_async(h, Qgain_dev, nu_dev, f_dev, 1, 1, stream);
+}
+
+int bfsm_collide_split(bfsm_handle h, double* Qgain_dev, double* nu_dev, const double* f_dev) {
+    int rc = bfsm_collide_split_async(h, Qgain_dev, nu_dev, f_dev, nullptr);
+    if (rc) return rc;
+    return bfsm_synchronize(h);
+}
+
+int bfsm_collide_bilinear_split_partial_async(bfsm_handle h, double* Qgain_dev, double* nu_dev, const double* g_dev,
+                                              const double* f_dev, int with_loss, void* stream) {
+    if (!h) return BFSM_ERR_INVALID;
+    BFSM_GUARDED(h,
+        DeviceGuard guard(h->desc.device);
+        int rc = enter(h, guard, stream);
+        if (rc) return rc;
+        if (!g_dev || !f_dev || !Qgain_dev) return fail(h, BFSM_ERR_INVALID, "null Qgain, g or f");
+        if (with_loss && !nu_dev) return fail(h, BFSM_ERR_INVALID, "null nu (it may be null only with with_loss = 0)");
+        if (h->desc.flags & BFSM_FLAG_EXACT_REDUCTIONS)
+            return fail(h, BFSM_ERR_UNSUPPORTED, "the bilinear form needs a handle without BFSM_FLAG_EXACT_REDUCTIONS (its antipodal merge assumes g = f)");
+        const size_t n = h->G;
+        if (ranges_overlap(Qgain_dev, g_dev, n) || ranges_overlap(Qgain_dev, f_dev, n) ||
+            (nu_dev && (ranges_overlap(nu_dev, g_dev, n) || ranges_overlap(nu_dev, f_dev, n) || ranges_overlap(nu_dev, Qgain_dev, n))))
+            return fail(h, BFSM_ERR_INVALID, "Qgain and nu must not overlap each other, g or f");
+        h->be.begin_eval();
+        h->with([&](auto& p) { p.collide_bilinear(Qgain_dev, g_dev, f_dev, with_loss != 0, with_loss ? nu_dev : nullptr); });
+        return leave(h, "bfsm_collide_bilinear_split");
+    )
+}
+
+// nu = Re IFFT(beta2 f_hat / G) alone: no gain work, any handle (Pipeline::loss_rate / GenericPipeline::loss_rate)
+int bfsm_loss_rate_async(bfsm_handle h, double* nu_dev, const double* f_dev, int n_batch, void* stream) {
+    if (!h) return BFSM_ERR_INVALID;
+    BFSM_GUARDED(h,
+        DeviceGuard g(h->desc.device);
+        int rc = enter(h, g, stream);
+        if (rc) return rc;
+        if (!f_dev || !nu_dev) return fail(h, BFSM_ERR_INVALID, "null f or nu");
+        int cap = 1;
+        h->with([&](auto& p) { cap = p.max_batch; });
+        if (n_batch < 1 || n_batch > cap)
+            return fail(h, BFSM_ERR_INVALID, "n_batch must be in [1, max_batch of the descriptor]");
+        if (ranges_overlap(nu_dev, f_dev, (size_t)n_batch * h->G)) return fail(h, BFSM_ERR_INVALID, "nu must not overlap f");
+        h->be.begin_eval();
+        for_batch(h, n_batch, [&](auto& p, int i0, int nb) { p.loss_rate(nu_dev + (size_t)i0 * h->G, f_dev + (size_t)i0 * h->G, nb); });
+        return leave(h, "bfsm_loss_rate");
+    )
 }
 
 // Q := P Q in place for n_batch consecutive arrays, any handle (the kernels of the BFSM_FLAG_CONSERVE route: bitwise the same)

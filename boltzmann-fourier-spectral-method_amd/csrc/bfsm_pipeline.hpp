@@ -460,18 +460,19 @@ struct Pipeline {
     // takes the plane-tile pipeline (the whole-direction kernels have no room for a second cube).  g_hat in fhat, f_hat in
     // fhat + G (init reserves two spectra).
     cx<T>* fhat_b() const { return fhat + plan.G(); }
-    void collide_bilinear(double* Q_dev, const double* g_dev, const double* f_dev, bool with_loss) {
+    // nu_dev: the split form (finish)
+    void collide_bilinear(double* Q_dev, const double* g_dev, const double* f_dev, bool with_loss, double* nu_dev = nullptr) {
         spectrum(g_dev, fhat, 1);
         if (f_dev == g_dev) {     // Q(f,f) through the bilinear kernels: one transform, both operands read the same spectrum
             const bool fu = fuse_reduce();
             gain_spectra(1, !fu, fhat);
-            finish(Q_dev, g_dev, with_loss, 1, fu, fhat);
+            finish(Q_dev, g_dev, with_loss, 1, fu, fhat, nu_dev);
             return;
         }
         spectrum(f_dev, fhat_b(), 1);
         const bool fu = fuse_reduce();
         gain_spectra(1, !fu, fhat_b());
-        finish(Q_dev, g_dev, with_loss, 1, fu, fhat_b());
+        finish(Q_dev, g_dev, with_loss, 1, fu, fhat_b(), nu_dev);
     }
 
     // The gain term of this shard from the spectra in fhat (and fhat2 for the bilinear form: the conj(alpha) operand) into qhat
@@ -560,8 +561,10 @@ struct Pipeline {
     // itself (half the bytes of summing Q_hat) and another rank adds the loss term.
     // from_slabs = true: the slab reduce is fused into the first tail kernel (after gain_partial(.., false)).
     // loss_hat (bilinear form): the spectrum the loss term convolves (f_hat); f_dev is then g, which multiplies it.
+    // nu_dev (gain / loss split, bfsm_collide_split*): Q_dev = Re IFFT(qhat), the gain alone, and with_loss adds
+    // nu_dev = Re IFFT(beta2 f_hat / G), the collision frequency, instead of subtracting its product with f; f_dev is not read.
     void finish(double* Q_dev, const double* f_dev, bool with_loss = true, int nb = 1, bool from_slabs = false,
-                const cx<T>* loss_hat = nullptr) {
+                const cx<T>* loss_hat = nullptr, double* nu_dev = nullptr) {
         const int N = plan.N;
         const double Gc = (double)plan.G() * cbytes() * nb;
         const size_t s_bs = (slab_count ? slab_count : 1) * plan.G();
@@ -571,6 +574,26 @@ struct Pipeline {
         be->template launch<K::TailInv, T>(N, with_loss ? 2 : 1, nb, ta, N);
         TailLineParams<T> tb{tg, tl, f_dev, Q_dev, tw, with_loss ? 1 : 0};
         be->mark(BFSM_K_TAIL, (with_loss ? 3.0 : 1.5) * Gc);
+        if (nu_dev && with_loss) {     // two complex arrays read, two real ones written: the bytes of the combined form
+            TailLineSplitParams<T> ts{};
+            static_cast<TailLineParams<T>&>(ts) = tb;
+            ts.f = nullptr;
+            ts.nu = nu_dev;
+            be->template launch<K::TailLine, T>(line_blocks(), nb, 1, ts, N);
+        } else be->template launch<K::TailLine, T>(line_blocks(), nb, 1, tb, N);
+    }
+
+    // nu = Re IFFT(beta2 f_hat / G) alone (bfsm_loss_rate_async): F1, the loss plane of the first tail kernel, then the
+    // gain-only tail line on that array.  No gain work; the direction shard plays no part.
+    void loss_rate(double* nu_dev, const double* f_dev, int nb = 1) {
+        const int N = plan.N;
+        const double Gc = (double)plan.G() * cbytes() * nb;
+        spectrum(f_dev, fhat, nb);
+        TailInvLossParams<T> ta{{nullptr, fhat, beta2, tg, (long long)(tl - tg), tw, nullptr, nullptr, nullptr, -1, plan.n2stride, 0}};
+        be->mark(BFSM_K_TAIL, 2.0 * Gc);
+        be->template launch<K::TailInv, T>(N, 1, nb, ta, N);
+        TailLineParams<T> tb{tl, tl, nullptr, nu_dev, tw, 0};
+        be->mark(BFSM_K_TAIL, 1.5 * Gc);
         be->template launch<K::TailLine, T>(line_blocks(), nb, 1, tb, N);
     }
 

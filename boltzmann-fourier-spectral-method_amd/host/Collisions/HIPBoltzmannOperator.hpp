@@ -52,6 +52,11 @@ public:
     // AbstractCollisionOperator; Q(f,f) is computeCollision(Q, f).
     void computeCollision(double* Q, const double* g, const double* f);
 
+    // Gain / loss split (include/bfsm.h, bfsm_collide_split): Qgain = Q+(f,f), nu = the collision frequency nu[f], so that
+    // Q = Qgain - f * nu; device pointers, blocking.  lossRate: nu alone, without any gain work (blocking).
+    void computeCollisionSplit(double* Qgain, double* nu, const double* f_in);
+    void lossRate(double* nu, const double* f_in);
+
     // Batch of n_batch <= setMaxBatch() distributions, [n_batch][Nvx*Nvy*Nvz] device arrays, one set of launches.
     void computeCollisionBatch(double* Q, const double* f_in, int n_batch);
     // Batch x direction shard: partial results of every member [with the loss term]; the caller sums Q over the ranks.

@@ -47,6 +47,15 @@ void BoltzmannOperator<HIP_Backend>::computeCollision(double* Q, const double* g
     check(bfsm_collide_bilinear(handle_, Q, g, f), "computeCollision (bilinear)");
 }
 
+void BoltzmannOperator<HIP_Backend>::computeCollisionSplit(double* Qgain, double* nu, const double* f_in) {
+    check(bfsm_collide_split(handle_, Qgain, nu, f_in), "computeCollisionSplit");
+}
+
+void BoltzmannOperator<HIP_Backend>::lossRate(double* nu, const double* f_in) {
+    check(bfsm_loss_rate_async(handle_, nu, f_in, 1, nullptr), "lossRate");
+    check(bfsm_synchronize(handle_), "lossRate");
+}
+
 void BoltzmannOperator<HIP_Backend>::computeCollisionBatch(double* Q, const double* f_in, int n_batch) {
     check(bfsm_collide_batch(handle_, Q, f_in, n_batch), "computeCollisionBatch");
 }

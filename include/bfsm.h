@@ -226,6 +226,40 @@ int bfsm_collide_bilinear_async(bfsm_handle h, double* Q_dev, const double* g_de
 int bfsm_collide_bilinear_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev,
                                         int with_loss, void* stream);
 
+/*
+ * Gain / loss split (new functionality; the presence of these symbols is the capability check, BFSM_VERSION stays 2).
+ * Every entry point above returns the combined Q = Q+ - f nu[f]; these return its two terms apart:
+ *     Qgain = Re IFFT(this handle's (partial) Q_gain_hat)   -- exactly what the combined call writes with with_loss = 0
+ *     nu    = Re IFFT(beta2 f_hat / G)                       -- the collision frequency nu[f]; written only if with_loss != 0
+ * so that Q = Qgain - f * nu (bilinear form: Q(g,f) = Qgain - g * nu, nu = nu[f]).  What an implicit or penalized time
+ * integrator needs: the loss step f <- (f + dt Qgain) / (1 + dt nu), a bound mu >= max nu, the diagonal -nu[f] of L_f, the
+ * time-step bound dt max nu.  Same kernels and bytes as the combined call; only the last tail kernel
+ * differs (two real arrays written instead of f read and one written).
+ *   - Qgain, nu, f (and g): device pointers to doubles, also on BFSM_F32 handles; batches are [n_batch][G] in all three
+ *     arrays, 1 <= n_batch <= max_batch, and member i is bitwise the single call on member i ON THE SAME HANDLE.
+ *   - with_loss = 0: nu may be NULL and is not touched.  On direction shards the caller sums Qgain over the ranks and
+ *     exactly one rank passes with_loss != 0 (nu does not depend on the shard).
+ *   - Qgain and nu must not overlap each other, f or g (BFSM_ERR_INVALID).
+ *   - bfsm_collide_split and bfsm_collide_split_async (the forms without _partial) need a handle that owns ALL directions.
+ *   - split is independent of the gain mode: faithful, BFSM_FLAG_EXACT_REDUCTIONS and BFSM_FLAG_HERMITIAN handles serve
+ *     Q(f,f); the bilinear split on an exact-reduction handle returns BFSM_ERR_UNSUPPORTED and leaves the outputs untouched,
+ *     like bfsm_collide_bilinear*.
+ *   - N = 16 handles evaluate split calls on the plane-tile pipeline (as with BFSM_FLAG_NO_SMALL_PATH).
+ *   - BFSM_FLAG_CONSERVE has NO effect on the split outputs: the projection P applies to Q, not to its two parts.  A caller
+ *     who wants PQ assembles Q = Qgain - f * nu and calls bfsm_conserve_async on it.
+ *   - bfsm_loss_rate_async computes nu alone, without any gain work (F1, beta2, one inverse transform), for n_batch
+ *     distributions on any handle, a direction shard included; nu must not overlap f.
+ *   - the _async forms are allocation-free after the first evaluation, graph-capturable and tracked by bfsm_synchronize like
+ *     the other _async entry points; bfsm_collide_split is blocking.
+ */
+int bfsm_collide_split(bfsm_handle h, double* Qgain_dev, double* nu_dev, const double* f_dev);
+int bfsm_collide_split_async(bfsm_handle h, double* Qgain_dev, double* nu_dev, const double* f_dev, void* stream);
+int bfsm_collide_split_batch_partial_async(bfsm_handle h, double* Qgain_dev, double* nu_dev, const double* f_dev, int n_batch,
+                                           int with_loss, void* stream);
+int bfsm_collide_bilinear_split_partial_async(bfsm_handle h, double* Qgain_dev, double* nu_dev, const double* g_dev,
+                                              const double* f_dev, int with_loss, void* stream);
+int bfsm_loss_rate_async(bfsm_handle h, double* nu_dev, const double* f_dev, int n_batch, void* stream);
+
 /* Q := PQ in place (the projection of BFSM_FLAG_CONSERVE, by the same kernels: bitwise the same result) for n_batch
  * consecutive arrays of G doubles, 1 <= n_batch <= max_batch, on any handle with or without the flag; enqueued on `stream`
  * like the other _async entry points (allocation-free, graph-capturable).  Null or misaligned Q, bad n_batch:

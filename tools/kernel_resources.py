@@ -31,5 +31,7 @@ for r, n in zip(rows, names):
     bi = " bilinear" if "BiParams" in n else ""       # the Q(g,f) instantiations (GainInvBiParams / GenFftBiParams)
     # kind 11 (GainLineAcc) has two bodies: the exact mode's (GainLineAccParams) and the faithful mode's segment sum
     bi += " GainLineSumParams" if "GainLineSumParams" in n else (" GainLineAccParams" if "GainLineAccParams" in n else "")
+    for tag in ("TailLineSplitParams", "TailInvLossParams", "GenCombineSplitParams"):     # the gain / loss split's instantiations
+        bi += " " + tag if tag in n else ""
     n = re.sub(r"^void bfsm::bfsm_kernel<\(bfsm::(S?K)\)(\d+), (\d+), (\w+),.*", r"\1 \2 N=\3 \4", n) + bi
     print(f"{r[1]:5d} {r[2]:5d} {r[3]:9d} {r[4]:10d} {r[5]:5d}  {n[:100]}")
