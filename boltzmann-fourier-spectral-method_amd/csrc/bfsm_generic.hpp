@@ -918,7 +918,7 @@ struct GenericPipeline {
     cx<T>* tail = nullptr;    // [2][G]: gain, loss
     cx<T>* a = nullptr;       // [2 * chunk][G]: A1, A2 interleaved per direction; P in the even members
     cx<T>* slab = nullptr;    // fused sequence: [groups][G] partial sums of one chunk
-    int slab_groups = 0;
+    int slab_groups = 0;      // the most groups any chunk of the plan launches
     cx<T>* tw[3] = {nullptr, nullptr, nullptr};
     cx<T>* phx = nullptr;
     cx<T>* phy = nullptr;
@@ -1033,9 +1033,15 @@ struct GenericPipeline {
         ok = ok && (tail = (cx<T>*)be->alloc((size_t)2 * max_batch * G * sizeof(cx<T>)));
         ok = ok && (a = (cx<T>*)be->alloc((size_t)mb * 2 * chunk * G * sizeof(cx<T>)));
         if (fused_ok()) {
-            slab_groups = groups_for(chunk);
+            // the largest launch of gain_chunk_fused: groups_for is not monotone, a shorter last chunk can need more groups
+            // than a full one (32 planes: 17 directions make 9 groups of 2, 16 directions 16 groups of 1)
+            slab_groups = 1;
+            for (const Chunk& ck : plan.chunks) {
+                const int g = groups_for(ck.n);
+                if (g > slab_groups) slab_groups = g;
+                plan.gen_slabs += g;
+            }
             ok = ok && (slab = (cx<T>*)be->alloc((size_t)mb * slab_groups * G * sizeof(cx<T>)));
-            for (const Chunk& ck : plan.chunks) plan.gen_slabs += groups_for(ck.n);
         }
         if (!ok) { err = "device allocation failed"; return BFSM_ERR_NOMEM; }
         return BFSM_OK;

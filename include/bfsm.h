@@ -123,8 +123,9 @@ typedef struct bfsm_desc {
     int device;               /* HIP device ordinal                       */
     long long dir_begin;      /* shard of the flattened quadrature directions b = r*n_sph + s handled by this   */
     long long dir_end;        /* handle: [dir_begin, dir_end).  0,0 = all directions (single-GPU behaviour).     */
-    int max_chunk;            /* directions resident at once (0 = default 1024: the whole shard in one pass when it
-                                 fits; scratch = 2 * chunk * G complex); bounds scratch, not results                 */
+    int max_chunk;            /* directions resident at once (0 = default: 1024 on the fused cubes, 256 on the size-
+                                 generic path: the whole shard in one pass when it fits; scratch = 2 * chunk * G
+                                 complex); bounds scratch, not results                                               */
     int flags;                /* BFSM_FLAG_*                              */
     int max_batch;            /* distributions per bfsm_collide_batch call (0/1 = single); scratch scales with it */
 } bfsm_desc;

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../boltzmann-fourier-spectral-method_amd/csrc/bfsm_pipeline.hpp"
@@ -392,16 +393,24 @@ struct RouteRec {
     int kind, precision, bilinear, mode, gx, gy;
     long long lds;
     int cat;
+    int groups, mgroups, n;    // plane-accumulate / accumulate launches of the fused sequence, see bfsm_emu_gen_routes
+    long long dir0;
 };
 
 struct RecordingBackend {
     std::vector<RouteRec> recs;
     uintptr_t next = (uintptr_t)1 << 32;
     int pend_kind = -1;
+    std::vector<std::pair<const void*, size_t>> allocs;      // what init asked for, by fake address
     void* alloc(size_t bytes) {
         void* p = reinterpret_cast<void*>(next);
         next += ((bytes + 4095) & ~(size_t)4095) + 4096;
+        allocs.push_back({p, bytes});
         return p;
+    }
+    size_t bytes_of(const void* p) const {
+        for (const auto& a : allocs) if (a.first == p) return a.second;
+        return 0;
     }
     void release(void*) {}
     void upload(void*, const void*, size_t) {}
@@ -412,15 +421,23 @@ struct RecordingBackend {
         if (gx <= 0 || gy <= 0) return;       // launch_any returns before it consumes the mark
         int mode = -1;
         if constexpr (std::is_base_of<bfsm::GenFftParams<T>, P>::value) mode = prm.mode;
+        int groups = -1, mgroups = -1, n = -1;
+        long long dir0 = -1;
+        if constexpr (kind == bfsm::GK::PlaneAcc) {           // member m, group g writes slab + (m * groups + g) * G
+            groups = prm.groups; mgroups = prm.groups; n = prm.n; dir0 = prm.dir0;
+        } else if constexpr (kind == bfsm::GK::Acc) {         // member m reads n arrays from p + m * p_mstride
+            const size_t G = (size_t)prm.nx * prm.ny * prm.nz;
+            groups = prm.n; mgroups = (int)(prm.p_mstride / G); n = prm.n; dir0 = prm.dir0;
+        }
         recs.push_back({(int)kind, (int)(sizeof(T) * 8), bfsm::gen_bilinear<P>::value ? 1 : 0, mode, gx, gy, (long long)lds,
-                        pend_kind});
+                        pend_kind, groups, mgroups, n, dir0});
         pend_kind = -1;
     }
 };
 
 // What bfsm_hip.hip runs on a size-generic handle for one call of the entry point `op` (see bfsm_emu_gen_routes)
 template <typename T>
-int gen_routes_t(const bfsm_desc* d, int op, int nb, std::vector<RouteRec>& out, int* info) {
+int gen_routes_t(const bfsm_desc* d, int op, int nb, std::vector<RouteRec>& out, int* info, long long* chunk_rows, int max_chunks) {
     RecordingBackend be;
     bfsm::GenericPipeline<T, RecordingBackend> p;
     std::string err;
@@ -430,6 +447,17 @@ int gen_routes_t(const bfsm_desc* d, int op, int nb, std::vector<RouteRec>& out,
     info[1] = p.plan.gen_moves;
     info[2] = p.plane_ok() ? 1 : 0;
     info[3] = p.fused_ok() ? 1 : 0;
+    // what init allocated: the A1 / A2 scratch is [mb][2 chunk][G], the slab buffer of the fused sequence [mb][slab_groups][G]
+    const size_t arr = p.G * sizeof(bfsm::cx<T>);
+    info[4] = p.slab_groups;
+    info[5] = p.chunk;
+    info[6] = (int)(be.bytes_of(p.a) / ((size_t)2 * p.chunk * arr));
+    info[7] = (int)(be.bytes_of(p.slab) / arr);
+    info[8] = (int)p.plan.chunks.size();
+    for (size_t i = 0; i < p.plan.chunks.size() && (int)i < max_chunks; ++i) {
+        chunk_rows[2 * i] = p.plan.chunks[i].dir0;
+        chunk_rows[2 * i + 1] = p.plan.chunks[i].n;
+    }
     double* Q = reinterpret_cast<double*>(be.alloc((size_t)nb * p.G * sizeof(double)));
     const double* f = reinterpret_cast<const double*>(be.alloc((size_t)nb * p.G * sizeof(double)));
     const double* g = reinterpret_cast<const double*>(be.alloc(p.G * sizeof(double)));
@@ -467,26 +495,33 @@ extern "C" {
 
 // Launch record of one call of a size-generic entry point, run by GenericPipeline's own host code with nothing executed.
 // op: 0 bfsm_collide, 1 bfsm_collide_batch (nb members), 2 bfsm_collide_partial_async without the loss term, 3
-// bfsm_collide_bilinear (g != f), 4 / 5 bfsm_fft3d forward / backward (batch nb).  rows (max_rows x 8 ints): GK kind,
+// bfsm_collide_bilinear (g != f), 4 / 5 bfsm_fft3d forward / backward (batch nb).  rows (max_rows x 12 ints): GK kind,
 // precision, bilinear params type, mode (-1: a params type without one), grid x, grid y, LDS bytes, counter category (-1:
-// not counted).  launches[BFSM_K_COUNT]: the kernel_launches bfsm_get_counters reports for that call under BFSM_FLAG_PROFILE.
-// info[4]: batch_together(), plan.gen_moves, plane_ok(), fused_ok().  Returns the launch count, or minus a status code.
-int bfsm_emu_gen_routes(const bfsm_desc* d, int op, int nb, int* rows, int max_rows, int* launches, int* info) {
+// not counted); then, for the plane-accumulate and accumulate launches (-1 otherwise): the slabs per member the launch
+// writes / sums, the distance between two members' slabs in arrays of G, the directions of the chunk (accumulate: the
+// arrays it sums) and the chunk's first direction.  launches[BFSM_K_COUNT]: the kernel_launches bfsm_get_counters reports
+// for that call under BFSM_FLAG_PROFILE.  info[9]: batch_together(), plan.gen_moves, plane_ok(), fused_ok(); then what init
+// allocated: slab_groups, chunk, the scratch multiplicity mb (members with A1 / A2 scratch of their own, from the size of
+// that allocation), the slab allocation in arrays of G, and the number of chunks.  chunk_rows (max_chunks x 2): first
+// direction and length of every chunk of the plan.  Returns the launch count, or minus a status code.
+int bfsm_emu_gen_routes(const bfsm_desc* d, int op, int nb, int* rows, int max_rows, int* launches, int* info,
+                        long long* chunk_rows, int max_chunks) {
     std::string err;
     int rc = bfsm::validate_desc(*d, err);
     if (rc) return -rc;
     if (bfsm::fused_grid(*d)) return -BFSM_ERR_UNSUPPORTED;
     std::vector<emu::RouteRec> recs;
-    rc = d->precision == BFSM_F64 ? emu::gen_routes_t<double>(d, op, nb, recs, info) : emu::gen_routes_t<float>(d, op, nb, recs, info);
+    rc = d->precision == BFSM_F64 ? emu::gen_routes_t<double>(d, op, nb, recs, info, chunk_rows, max_chunks)
+                                   : emu::gen_routes_t<float>(d, op, nb, recs, info, chunk_rows, max_chunks);
     if (rc) return -rc;
     for (int k = 0; k < BFSM_K_COUNT; ++k) launches[k] = 0;
     for (size_t i = 0; i < recs.size(); ++i) {
         const emu::RouteRec& r = recs[i];
         if (r.cat >= 0 && r.cat < BFSM_K_COUNT) launches[r.cat] += 1;
         if ((int)i < max_rows) {
-            int* o = rows + 8 * i;
+            int* o = rows + 12 * i;
             o[0] = r.kind; o[1] = r.precision; o[2] = r.bilinear; o[3] = r.mode; o[4] = r.gx; o[5] = r.gy;
-            o[6] = (int)r.lds; o[7] = r.cat;
+            o[6] = (int)r.lds; o[7] = r.cat; o[8] = r.groups; o[9] = r.mgroups; o[10] = r.n; o[11] = (int)r.dir0;
         }
     }
     return (int)recs.size();

@@ -39,7 +39,8 @@ def _typed(L):
     ip = ctypes.POINTER(ctypes.c_int)
     L.bfsm_emu_plan.argtypes = [ctypes.POINTER(capi.Desc), ip, ctypes.c_int, ip, ctypes.c_int, ip]
     L.bfsm_emu_plan.restype = ctypes.c_int
-    L.bfsm_emu_gen_routes.argtypes = [ctypes.POINTER(capi.Desc), ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip, ip]
+    L.bfsm_emu_gen_routes.argtypes = [ctypes.POINTER(capi.Desc), ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip, ip,
+                                      ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
     L.bfsm_emu_gen_routes.restype = ctypes.c_int
     return L
 
@@ -150,13 +151,14 @@ class EmuOperator:
         Q.copy_(torch.from_numpy(out))
 
 
-def collide_batch(fs, gl, sph, gamma, b_gamma, L, precision=64, max_chunk=0, flags=0):
-    """fs: [n_batch][nvx][nvy][nvz]; one emulated bfsm_collide_batch call.  Returns Q with the same shape."""
+def collide_batch(fs, gl, sph, gamma, b_gamma, L, precision=64, max_chunk=0, flags=0, dir_range=(0, 0), gpu_groups=False):
+    """fs: [n_batch][nvx][nvy][nvz]; one emulated bfsm_collide_batch call (on a direction shard: the shard's gain and the
+    loss term).  gpu_groups: as in collide.  Returns Q with the same shape."""
     fs = np.ascontiguousarray(fs, dtype=np.float64)
     nb = fs.shape[0]
     nv = fs.shape[1] if fs.shape[1] == fs.shape[2] == fs.shape[3] else fs.shape[1:]
-    d, keep = make_desc(nv, gl, sph, gamma, b_gamma, L, precision, (0, 0), max_chunk, flags, max_batch=nb)
-    L_ = lib()
+    d, keep = make_desc(nv, gl, sph, gamma, b_gamma, L, precision, dir_range, max_chunk, flags, max_batch=nb)
+    L_ = lib_gpu_groups() if gpu_groups else lib()
     dp = ctypes.POINTER(ctypes.c_double)
     if not hasattr(L_.bfsm_emu_collide_batch, "_typed"):
         from bfsm import capi
@@ -219,26 +221,36 @@ GK_NAMES = ("Fft", "Acc", "Combine", "FftBig", "Plane", "Line3", "PlaneAcc", "Pl
 GEN_MODES = {-1: None, 0: "PLAIN", 1: "PHASE", 2: "PRODUCT", 3: "REAL", 4: "BETA2", 5: "TAIL2"}
 
 
-def gen_routes(shape, n_gl, n_sph, precision=64, op="collide", nb=1, max_chunk=0, dir_range=(0, 0), max_batch=0):
+def gen_routes(shape, n_gl, n_sph, precision=64, op="collide", nb=1, max_chunk=0, dir_range=(0, 0), max_batch=0, gpu_groups=True):
     """Launches of one call of a size-generic entry point (op: a key of ROUTE_OPS), recorded by GenericPipeline's own host
-    code with the GPU's plane-accumulate grouping and nothing executed.  Returns (launches, kernel_launches, info):
-    launches = list of dicts (kind, precision, bilinear, mode, grid, lds, cat), kernel_launches = the 6 per-category
-    counts bfsm_get_counters reports under BFSM_FLAG_PROFILE, info = dict(together, gen_moves, plane, fused) of the
-    pipeline (batch_together(), plan.gen_moves, plane_ok(), fused_ok())."""
+    code with nothing executed and no scratch allocated.  gpu_groups: the GPU's plane-accumulate grouping (512 workgroups
+    per launch, lib_gpu_groups) or the emulator's (24, lib).  Returns (launches, kernel_launches, info):
+    launches = list of dicts (kind, precision, bilinear, mode, grid, lds, cat; and for the PlaneAcc / Acc launches groups =
+    the slabs per member the launch writes / sums, mgroups = the distance between two members' slabs in arrays of G, n =
+    the directions of the chunk, dir0 = its first direction), kernel_launches = the 6 per-category counts
+    bfsm_get_counters reports under BFSM_FLAG_PROFILE, info = dict(together, gen_moves, plane, fused) of the pipeline
+    (batch_together(), plan.gen_moves, plane_ok(), fused_ok()) plus what init allocated: slab_groups, chunk (directions
+    resident at once), mb (members with scratch of their own), slab_arrays (the slab allocation in arrays of G) and chunks =
+    [(first direction, length)] of the plan."""
     gl = (np.linspace(1.0, 2.0, n_gl), np.ones(n_gl))
-    sph = (np.ones(n_sph), np.zeros(n_sph), np.zeros(n_sph), np.ones(n_sph))
+    # nothing executes, so the rule's values do not matter: null vectors keep init's phase tables cheap (cos 0, sin 0)
+    sph = (np.zeros(n_sph), np.zeros(n_sph), np.zeros(n_sph), np.ones(n_sph))
     d, keep = make_desc(tuple(shape), gl, sph, 0.0, 1.0, 11.0, precision, dir_range, max_chunk, 0, max_batch)
-    cap = 4096
-    rows = (ctypes.c_int * (8 * cap))()
+    cap, ccap = 4096, 1024
+    rows = (ctypes.c_int * (12 * cap))()
     kl = (ctypes.c_int * 6)()
-    info = (ctypes.c_int * 4)()
-    n = lib_gpu_groups().bfsm_emu_gen_routes(ctypes.byref(d), ROUTE_OPS[op], nb, rows, cap, kl, info)
+    info = (ctypes.c_int * 9)()
+    crows = (ctypes.c_longlong * (2 * ccap))()
+    n = (lib_gpu_groups() if gpu_groups else lib()).bfsm_emu_gen_routes(ctypes.byref(d), ROUTE_OPS[op], nb, rows, cap, kl, info,
+                                                                        crows, ccap)
     if n < 0:
         raise ValueError(f"bfsm_emu_gen_routes rejected {shape} {precision} {op}: rc={-n}")
-    assert n <= cap
+    assert n <= cap and info[8] <= ccap
     out = []
     for i in range(n):
-        r = rows[8 * i:8 * i + 8]
+        r = rows[12 * i:12 * i + 12]
         out.append(dict(kind=GK_NAMES[r[0]], precision=r[1], bilinear=bool(r[2]), mode=GEN_MODES[r[3]],
-                        grid=(r[4], r[5]), lds=r[6], cat=r[7]))
-    return out, tuple(kl), dict(together=bool(info[0]), gen_moves=info[1], plane=bool(info[2]), fused=bool(info[3]))
+                        grid=(r[4], r[5]), lds=r[6], cat=r[7], groups=r[8], mgroups=r[9], n=r[10], dir0=r[11]))
+    return out, tuple(kl), dict(together=bool(info[0]), gen_moves=info[1], plane=bool(info[2]), fused=bool(info[3]),
+                                slab_groups=info[4], chunk=info[5], mb=info[6], slab_arrays=info[7],
+                                chunks=[(crows[2 * i], crows[2 * i + 1]) for i in range(info[8])])

@@ -369,6 +369,16 @@ def test_randomised_plans_against_the_oracle(oracle):
     ((8, 256, 4), 1, 6, 64, 1e-12, {}),                      # ... on 256-point y lines, exactly at the 40 KiB plane cap
     # the GPU's plane-accumulate grouping (512 workgroups): 6 groups of 5 directions across radial nodes of 6
     ((100, 4, 6), 5, 6, 64, 1e-12, {"gpu_groups": True}),
+    # chunks of the fused sequence that launch different numbers of plane-accumulate groups (groups_for is not monotone):
+    # a last chunk with MORE groups than a full one -- 2 then 3 under the emulator's grouping, 9 then 16 and 20 then 32
+    # under the GPU's -- which the slab buffer has to hold (tests/test_generic_chunks.py checks every such plan)
+    ((8, 4, 12), 3, 12, 64, 1e-12, {"dir_range": (0, 7), "max_chunk": 4}),
+    ((8, 4, 12), 3, 12, 32, 2e-5, {"dir_range": (0, 7), "max_chunk": 4}),
+    ((32, 8, 8), 6, 6, 64, 1e-12, {"dir_range": (0, 33), "max_chunk": 17, "gpu_groups": True}),
+    ((16, 8, 6), 6, 12, 64, 1e-12, {"max_chunk": 40, "gpu_groups": True}),
+    ((16, 8, 6), 6, 12, 32, 2e-5, {"max_chunk": 32, "gpu_groups": True}),    # a last chunk with fewer groups: 32, 32, 8
+    ((12, 6, 10), 4, 6, 32, 2e-5, {"max_chunk": 1}),                         # one direction at a time
+    ((16, 8, 6), 3, 12, 64, 1e-12, {"max_chunk": 7}),                        # a last chunk of one direction: 5 x 7 + 1
 ])
 def test_size_generic_path_matches_oracle(oracle, shape, n_gl, n_sph, prec, tol, kw):
     """Grids outside the fused pipeline's cubes (csrc/bfsm_generic.hpp: one mixed-radix Stockham pass per axis, pointwise
@@ -388,20 +398,34 @@ def test_size_generic_path_matches_oracle(oracle, shape, n_gl, n_sph, prec, tol,
         assert np.abs(Q - Qo).max() <= tol * np.abs(Qo).max()
 
 
-@pytest.mark.parametrize("shape,max_chunk", [((16, 8, 6), 0), ((16, 8, 6), 7), ((8, 14, 6), 0)])
+# test_size_generic_batch_of_distributions: (shape, max_chunk) -> rule, shard and grouping where they are not the default
+BATCH_PLANS = {
+    # a last chunk with more plane-accumulate groups than a full one: 2 then 3 (emulator grouping), 9 then 16, 20 then 32
+    ((8, 4, 12), 4): dict(n_gl=3, n_sph=12, dir_range=(0, 7)),
+    ((32, 8, 8), 17): dict(n_gl=6, n_sph=6, dir_range=(0, 33), gpu_groups=True, members=2),
+    ((16, 8, 6), 40): dict(n_gl=6, n_sph=12, gpu_groups=True, members=2),
+    # ((16, 8, 6), 7): a last chunk with fewer groups (2, 2, 1); ((16, 8, 6), 17): a last chunk of one direction (18 = 17 + 1)
+}
+
+
+@pytest.mark.parametrize("shape,max_chunk", [((16, 8, 6), 0), ((16, 8, 6), 7), ((8, 14, 6), 0), ((8, 4, 12), 4), ((32, 8, 8), 17),
+                                             ((16, 8, 6), 40), ((16, 8, 6), 1), ((16, 8, 6), 17)])
 def test_size_generic_batch_of_distributions(oracle, shape, max_chunk):
     """A batch on the size-generic path: the fused sequence takes all members through every launch (own f_hat, scratch,
     slabs and Q_hat per member), the other sequences one member after the other -- either way bitwise the single
     evaluations, and the oracle's result."""
+    plan = BATCH_PLANS.get((shape, max_chunk), {})
     rng = np.random.default_rng(11)
-    fs = rng.random((3,) + shape) + 0.1
-    gl = oracle.gauss_legendre(3, 0.0, R)
-    sph = oracle.spherical_design(6)
-    Qb = E.collide_batch(fs, gl, sph, 0.5, 0.3, 11.0, max_chunk=max_chunk)
-    for i in range(3):
-        Qi, _ = E.collide(fs[i], gl, sph, 0.5, 0.3, 11.0, 64, max_chunk=max_chunk)
+    nb = plan.get("members", 3)
+    fs = rng.random((nb,) + shape) + 0.1
+    gl = oracle.gauss_legendre(plan.get("n_gl", 3), 0.0, R)
+    sph = oracle.spherical_design(plan.get("n_sph", 6))
+    kw = dict(max_chunk=max_chunk, dir_range=plan.get("dir_range", (0, 0)), gpu_groups=plan.get("gpu_groups", False))
+    Qb = E.collide_batch(fs, gl, sph, 0.5, 0.3, 11.0, **kw)
+    for i in range(nb):
+        Qi, _ = E.collide(fs[i], gl, sph, 0.5, 0.3, 11.0, 64, **kw)
         assert np.array_equal(Qb[i], Qi)
-        Qo = oracle.collide(fs[i], gl, sph, 0.5, 0.3, 11.0)
+        Qo = oracle.collide(fs[i], gl, sph, 0.5, 0.3, 11.0, dir_range=plan.get("dir_range"))
         assert np.abs(Qb[i] - Qo).max() <= 1e-12 * np.abs(Qo).max()
 
 
