@@ -42,6 +42,8 @@ def _typed(L):
     L.bfsm_emu_gen_routes.argtypes = [ctypes.POINTER(capi.Desc), ctypes.c_int, ctypes.c_int, ip, ctypes.c_int, ip, ip,
                                       ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
     L.bfsm_emu_gen_routes.restype = ctypes.c_int
+    L.bfsm_emu_collide_batch.argtypes = [ctypes.POINTER(capi.Desc), dp, dp, dp, ctypes.c_int]
+    L.bfsm_emu_collide_batch.restype = ctypes.c_int
     return L
 
 
@@ -90,12 +92,12 @@ def fft3d(a, sign, precision=64):
     return buf
 
 
-def plan(nv, n_gl, n_sph, precision=64, dir_range=(0, 0), max_chunk=0, flags=0, sph=None):
+def plan(nv, n_gl, n_sph, precision=64, dir_range=(0, 0), max_chunk=0, flags=0, sph=None, max_batch=0):
     """Returns (chunks, segments): chunk rows (n_seg, dir0, n, per_group, seg0), segment rows (chunk, d0, n, r)."""
     gl = (np.ones(n_gl), np.ones(n_gl))
     if sph is None:
         sph = (np.ones(n_sph), np.zeros(n_sph), np.zeros(n_sph), np.ones(n_sph))
-    d, keep = make_desc(nv, gl, sph, 0.0, 1.0, 1.0, precision, dir_range, max_chunk, flags)
+    d, keep = make_desc(nv, gl, sph, 0.0, 1.0, 1.0, precision, dir_range, max_chunk, flags, max_batch)
     crow = (ctypes.c_int * (5 * 4096))()
     srow = (ctypes.c_int * (5 * 65536))()
     nseg = ctypes.c_int()
@@ -151,20 +153,17 @@ class EmuOperator:
         Q.copy_(torch.from_numpy(out))
 
 
-def collide_batch(fs, gl, sph, gamma, b_gamma, L, precision=64, max_chunk=0, flags=0, dir_range=(0, 0), gpu_groups=False):
+def collide_batch(fs, gl, sph, gamma, b_gamma, L, precision=64, max_chunk=0, flags=0, dir_range=(0, 0), gpu_groups=False,
+                  max_batch=None):
     """fs: [n_batch][nvx][nvy][nvz]; one emulated bfsm_collide_batch call (on a direction shard: the shard's gain and the
-    loss term).  gpu_groups: as in collide.  Returns Q with the same shape."""
+    loss term) on a handle created for max_batch members (default: n_batch).  gpu_groups: as in collide.  Returns Q with the
+    same shape."""
     fs = np.ascontiguousarray(fs, dtype=np.float64)
     nb = fs.shape[0]
     nv = fs.shape[1] if fs.shape[1] == fs.shape[2] == fs.shape[3] else fs.shape[1:]
-    d, keep = make_desc(nv, gl, sph, gamma, b_gamma, L, precision, dir_range, max_chunk, flags, max_batch=nb)
+    d, keep = make_desc(nv, gl, sph, gamma, b_gamma, L, precision, dir_range, max_chunk, flags, max_batch=max_batch or nb)
     L_ = lib_gpu_groups() if gpu_groups else lib()
     dp = ctypes.POINTER(ctypes.c_double)
-    if not hasattr(L_.bfsm_emu_collide_batch, "_typed"):
-        from bfsm import capi
-        L_.bfsm_emu_collide_batch.argtypes = [ctypes.POINTER(capi.Desc), dp, dp, dp, ctypes.c_int]
-        L_.bfsm_emu_collide_batch.restype = ctypes.c_int
-        L_.bfsm_emu_collide_batch._typed = True
     Q = np.empty_like(fs)
     rc = L_.bfsm_emu_collide_batch(ctypes.byref(d), fs.ctypes.data_as(dp), Q.ctypes.data_as(dp), None, nb)
     if rc:
