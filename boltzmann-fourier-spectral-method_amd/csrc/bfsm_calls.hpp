@@ -1,0 +1,50 @@
+// bfsm_calls.hpp -- what each entry point of include/bfsm.h launches, stated once: sequences of the primitives of Pipeline
+// (bfsm_pipeline.hpp) and GenericPipeline (bfsm_generic.hpp), as function templates over the pipeline type.  Pure C++17, no
+// HIP: bfsm_hip.hip calls them from its extern "C" bodies, the host emulator and its launch recorder (tests/emu) call the same
+// functions, so a test of a sequence is a test of the library's.
+#pragma once
+#include <cstddef>
+
+namespace bfsm {
+
+// A batch through fn(first member, members): together where the pipeline's launches cover a batch, else one by one
+template <class Pipe, class F>
+void for_batch(Pipe& p, int n_batch, F&& fn) {
+    if (p.batch_together()) fn(0, n_batch);
+    else for (int i = 0; i < n_batch; ++i) fn(i, 1);
+}
+
+// Q = gain of the shard [- loss] for n_batch distributions (bfsm_collide*_async, bfsm_collide_batch*_async): the
+// whole-direction kernels where the handle has them (N = 16, one evaluation), otherwise the gain kernels, then the tail.
+// fuse: the slab reduce runs inside the first tail kernel (qhat is not written then); the library passes p.fuse_reduce().
+template <class Pipe>
+void collide(Pipe& p, double* Q, const double* f, int n_batch, bool with_loss, bool fuse) {
+    const size_t G = p.plan.G();
+    for_batch(p, n_batch, [&](int i0, int nb) {
+        const size_t o = (size_t)i0 * G;
+        if (p.small_path(nb)) { p.collide_small(Q + o, f + o, with_loss); return; }
+        p.gain_partial(f + o, nb, !fuse);
+        p.finish(Q + o, f + o, with_loss, nb, fuse);
+    });
+}
+
+// The same with the two terms of the tail kept apart (bfsm_collide_split*_async): Qgain = the gain alone and, with_loss,
+// nu = the collision frequency.  N = 16 takes the plane-tile pipeline.
+template <class Pipe>
+void collide_split(Pipe& p, double* Qgain, double* nu, const double* f, int n_batch, bool with_loss, bool fuse) {
+    const size_t G = p.plan.G();
+    for_batch(p, n_batch, [&](int i0, int nb) {
+        const size_t o = (size_t)i0 * G;
+        p.gain_partial(f + o, nb, !fuse);
+        p.finish(Qgain + o, nullptr, with_loss, nb, fuse, nullptr, with_loss ? nu + o : nullptr);
+    });
+}
+
+// nu alone (bfsm_loss_rate_async)
+template <class Pipe>
+void loss_rate(Pipe& p, double* nu, const double* f, int n_batch) {
+    const size_t G = p.plan.G();
+    for_batch(p, n_batch, [&](int i0, int nb) { p.loss_rate(nu + (size_t)i0 * G, f + (size_t)i0 * G, nb); });
+}
+
+}  // namespace bfsm

@@ -176,6 +176,12 @@ BFSM_HD void body_cons_small(const ConsParams& p, Ctx& ctx) {
         ctx.template st_at<false>(row, q * SZ, cons_subtract(p, q, ctx.template ld_at<false>(row, q * SZ), lam));
 }
 
+// the body of kernel `kind` on one workgroup (a macro for the reason given at BFSM_RUN_BODY, bfsm_pipeline.hpp)
+#define BFSM_RUN_CONS_BODY(kind, prm, ctx)                           \
+    if constexpr (kind == CK::Moments) body_cons_moments(prm, ctx);  \
+    else if constexpr (kind == CK::Apply) body_cons_apply(prm, ctx); \
+    else if constexpr (kind == CK::Small) body_cons_small(prm, ctx);
+
 // Host side: the constants (long double, at bfsm_create) and the launch sequence.  Beside the pipelines, not inside them:
 // the entry points call apply() on the same backend and stream after the pipeline's launches.  `Backend` supplies alloc /
 // release / mark and  template <CK kind> void launch_cons(int grid_x, int grid_y, const ConsParams&).

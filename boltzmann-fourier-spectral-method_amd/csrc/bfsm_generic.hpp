@@ -874,6 +874,20 @@ BFSM_HD void body_gen_combine(const P& prm, Ctx& ctx) {
 enum class GK { Fft, Acc, Combine, FftBig, Plane, Line3, PlaneAcc, PlanePair, Fft8, FftBig8, Line38 };   // ...8: 8 lines per workgroup   // FftBig: Fft + the radix-7 / 11 / 13 passes; Plane: y and z
                                                                       // pass fused; Line3 / PlaneAcc: the fused sequence
 
+// the body of kernel `kind` on one workgroup (a macro for the reason given at BFSM_RUN_BODY, bfsm_pipeline.hpp)
+#define BFSM_RUN_GEN_BODY(kind, T, prm, ctx)                                       \
+    if constexpr (kind == GK::Fft) body_gen_fft<T, false, GEN_C>(prm, ctx);        \
+    else if constexpr (kind == GK::FftBig) body_gen_fft<T, true, GEN_C>(prm, ctx); \
+    else if constexpr (kind == GK::Plane) body_gen_plane<T>(prm, ctx);             \
+    else if constexpr (kind == GK::Acc) body_gen_acc<T>(prm, ctx);                 \
+    else if constexpr (kind == GK::Combine) body_gen_combine<T>(prm, ctx);         \
+    else if constexpr (kind == GK::Line3) body_gen_line3<T, GEN_C>(prm, ctx);      \
+    else if constexpr (kind == GK::PlaneAcc) body_gen_plane_acc<T>(prm, ctx);      \
+    else if constexpr (kind == GK::PlanePair) body_gen_plane_pair<T>(prm, ctx);    \
+    else if constexpr (kind == GK::Fft8) body_gen_fft<T, false, 8>(prm, ctx);      \
+    else if constexpr (kind == GK::FftBig8) body_gen_fft<T, true, 8>(prm, ctx);    \
+    else if constexpr (kind == GK::Line38) body_gen_line3<T, 8>(prm, ctx);
+
 inline bool gen_factor(int n, std::vector<int>& radix) {
     radix.clear();
     if (n < 2 || n > GEN_MAX_N) return false;

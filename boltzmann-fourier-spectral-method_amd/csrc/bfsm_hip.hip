@@ -12,6 +12,7 @@
 #include "bfsm_pipeline.hpp"
 #include "bfsm_generic.hpp"
 #include "bfsm_conserve.hpp"
+#include "bfsm_calls.hpp"
 
 #ifndef BFSM_F32_N64_WAVES
 #define BFSM_F32_N64_WAVES 4
@@ -329,20 +330,6 @@ extern "C" int bfsm_debug_counters(unsigned long long* out32, int reset) {
 }
 #endif
 
-template <K kind, int N>
-constexpr int kernel_threads() {
-    if (kind == K::GainInv && pair_tile<N>()) return pair_threads<N>();      // two tiles side by side (N = 32)
-    return kind == K::Reduce ? 256 : (is_line_kind(kind) ? Wg<N>::LINE_THREADS : Wg<N>::THREADS);
-}
-template <K kind, int N, typename T>
-constexpr size_t kernel_lds_bytes() {
-    if (kind == K::GainInv && pair_tile<N>()) return pair_lds_bytes<N, T>();
-    if (kind == K::GainInv && ka_xlane<N, T>()) return ka_xlane_lds_bytes<N, T>();
-    if (kind == K::GainFwd) return kc_lds_bytes<N, T>();
-    if (kind == K::GainInvNyq) return gain_inv_lds_bytes<N, T>();
-    return kind == K::Reduce ? 0 : (is_line_kind(kind) ? line_lds_bytes<N, T>() : tile_lds_bytes<N, T>());
-}
-
 // Minimum waves per SIMD the register allocator must leave room for.  N=64: a 512-thread workgroup is 2 waves per
 // SIMD and its 65 KiB tile lets two workgroups share a CU's 160 KiB LDS, so ask for 4 (<= 128 VGPRs).
 template <K kind, int N, typename T>
@@ -358,26 +345,7 @@ template <K kind, int N, typename T, class P>
 __global__ void __launch_bounds__((kernel_threads<kind, N>()), (kernel_min_waves<kind, N, T>())) bfsm_kernel(const P prm) {
     extern __shared__ __align__(16) unsigned char bfsm_smem[];
     DevCtx ctx{bfsm_smem};
-    if constexpr (kind == K::TileFwdReal) body_tile_fwd_real<N, T>(prm, ctx);
-    else if constexpr (kind == K::LineFwd) body_line<N, -1, T>(prm, ctx);
-    else if constexpr (kind == K::LineInv) body_line<N, +1, T>(prm, ctx);
-    else if constexpr (kind == K::TileFwd) body_tile_c2c<N, -1, T>(prm, ctx);
-    else if constexpr (kind == K::TileInv) body_tile_c2c<N, +1, T>(prm, ctx);
-    else if constexpr (kind == K::GainInv && pair_tile<N>()) body_gain_inv_pair<N, T>(prm, ctx);
-    else if constexpr (kind == K::GainInv) body_gain_inv<N, T>(prm, ctx);
-    else if constexpr (kind == K::GainLine) body_gain_line<N, T>(prm, ctx);
-    else if constexpr (kind == K::GainFwd) body_gain_fwd<N, T>(prm, ctx);
-    else if constexpr (kind == K::Reduce) body_reduce<N, T>(prm, ctx);
-    else if constexpr (kind == K::TailInv) body_tail_inv<N, T>(prm, ctx);
-    else if constexpr (kind == K::TailLine) body_tail_line<N, T>(prm, ctx);
-    else if constexpr (kind == K::GainLineAcc) body_gain_line_acc<N, T>(prm, ctx);
-    else if constexpr (kind == K::NyqRows) body_nyq_rows<N, T>(prm, ctx);
-    else if constexpr (kind == K::GainLineAccH) body_gain_line_acc_h<N, T>(prm, ctx);
-    else if constexpr (kind == K::GainInvNyq) {          // only launched where nyq_rides_along<N>()
-        if constexpr (nyq_rides_along<N>()) body_gain_inv_nyq<N, T>(prm, ctx);
-    } else if constexpr (kind == K::GainInvTwo) {          // only launched on ab_interleaved geometries (Hermitian mode)
-        if constexpr (ab_interleaved<N, T>()) body_gain_inv<N, T, false>(prm, ctx);
-    }
+    BFSM_RUN_BODY(kind, N, T, prm, ctx)
 }
 
 // size-generic path (bfsm_generic.hpp): runtime sizes, 256 threads, dynamic LDS
@@ -385,17 +353,7 @@ template <GK kind, typename T, class P>
 __global__ void __launch_bounds__(GEN_THREADS) bfsm_gen_kernel(const P prm) {
     extern __shared__ __align__(16) unsigned char bfsm_smem[];
     DevCtx ctx{bfsm_smem};
-    if constexpr (kind == GK::Fft) body_gen_fft<T, false, GEN_C>(prm, ctx);
-    else if constexpr (kind == GK::FftBig) body_gen_fft<T, true, GEN_C>(prm, ctx);
-    else if constexpr (kind == GK::Plane) body_gen_plane<T>(prm, ctx);
-    else if constexpr (kind == GK::Acc) body_gen_acc<T>(prm, ctx);
-    else if constexpr (kind == GK::Combine) body_gen_combine<T>(prm, ctx);
-    else if constexpr (kind == GK::Line3) body_gen_line3<T, GEN_C>(prm, ctx);
-    else if constexpr (kind == GK::PlaneAcc) body_gen_plane_acc<T>(prm, ctx);
-    else if constexpr (kind == GK::PlanePair) body_gen_plane_pair<T>(prm, ctx);
-    else if constexpr (kind == GK::Fft8) body_gen_fft<T, false, 8>(prm, ctx);
-    else if constexpr (kind == GK::FftBig8) body_gen_fft<T, true, 8>(prm, ctx);
-    else if constexpr (kind == GK::Line38) body_gen_line3<T, 8>(prm, ctx);
+    BFSM_RUN_GEN_BODY(kind, T, prm, ctx)
 }
 
 // N = 16 whole-direction kernels: 256 threads, two padded cubes of LDS
@@ -403,8 +361,7 @@ template <SK kind, typename T, class P>
 __global__ void __launch_bounds__(SMALL_THREADS) bfsm_small_kernel(const P prm) {
     extern __shared__ __align__(16) unsigned char bfsm_smem[];
     DevCtx ctx{bfsm_smem};
-    if constexpr (kind == SK::Gain) body_small_gain<T>(prm, ctx);
-    else if constexpr (kind == SK::Reduce) body_small_reduce<T>(prm, ctx);
+    BFSM_RUN_SMALL_BODY(kind, T, prm, ctx)
 }
 
 // conservative projection (bfsm_conserve.hpp): 256 threads, 10 KiB of LDS
@@ -412,9 +369,7 @@ template <CK kind>
 __global__ void __launch_bounds__(CONS_THREADS) bfsm_cons_kernel(const ConsParams prm) {
     extern __shared__ __align__(16) unsigned char bfsm_smem[];
     DevCtx ctx{bfsm_smem};
-    if constexpr (kind == CK::Moments) body_cons_moments(prm, ctx);
-    else if constexpr (kind == CK::Apply) body_cons_apply(prm, ctx);
-    else if constexpr (kind == CK::Small) body_cons_small(prm, ctx);
+    BFSM_RUN_CONS_BODY(kind, prm, ctx)
 }
 
 // ---- HIP backend -----------------------------------------------------------------------------------------------
@@ -494,7 +449,7 @@ struct HipBackend {
     void launch_small(int gx, const P& prm) {
         static std::atomic<unsigned long long> opted{0};
         launch_any(reinterpret_cast<const void*>(bfsm_small_kernel<kind, T, P>), gx, 1, 1, SMALL_THREADS,
-                   kind == SK::Reduce ? 256 * sizeof(double) : small_lds_bytes<T>(), &prm, opted);
+                   small_kernel_lds_bytes<kind, T>(), &prm, opted);
     }
 
     // size-generic path; the LDS need depends on the transformed axis, so the opt-in asks for the whole CU's 160 KiB
@@ -514,18 +469,7 @@ struct HipBackend {
     template <K kind, typename T, class P>
     void launch(int gx, int gy, int gz, const P& prm, int N) {
         if (gx <= 0 || gy <= 0 || gz <= 0) return;
-        switch (N) {
-            case 16: launch_n<kind, 16, T>(gx, gy, gz, prm); break;
-            case 24: launch_n<kind, 24, T>(gx, gy, gz, prm); break;
-            case 32: launch_n<kind, 32, T>(gx, gy, gz, prm); break;
-            case 40: launch_n<kind, 40, T>(gx, gy, gz, prm); break;
-            case 48: launch_n<kind, 48, T>(gx, gy, gz, prm); break;
-            case 80: launch_n<kind, 80, T>(gx, gy, gz, prm); break;
-            case 64: launch_n<kind, 64, T>(gx, gy, gz, prm); break;
-            case 96: launch_n<kind, 96, T>(gx, gy, gz, prm); break;
-            case 128: launch_n<kind, 128, T>(gx, gy, gz, prm); break;
-            default: break;
-        }
+        for_fused_n(N, [&](auto n) { launch_n<kind, decltype(n)::value, T>(gx, gy, gz, prm); });
     }
 
     void destroy_events() {
@@ -598,15 +542,6 @@ static int check_hip(bfsm_plan* h, const char* where) {
                     " at bfsm_hip.hip:" + std::to_string(h->be.first_error_line) + " (during " + where + ")";
     h->be.first_error = hipSuccess;
     return fail(h, BFSM_ERR_HIP, m);
-}
-
-// a batch through `fn(pipeline, first member, members)`: together where the pipeline's launches cover a batch, else one by one
-template <class F>
-static void for_batch(bfsm_plan* h, int n_batch, F&& fn) {
-    bool together = true;
-    if (h->g64 || h->g32) h->with([&](auto& p) { together = p.batch_together(); });
-    if (together) h->with([&](auto& p) { fn(p, 0, n_batch); });
-    else for (int i = 0; i < n_batch; ++i) h->with([&](auto& p) { fn(p, i, 1); });
 }
 
 extern "C" {
@@ -790,20 +725,7 @@ int bfsm_collide_batch_partial_async(bfsm_handle h, double* Q_dev, const double*
             return fail(h, BFSM_ERR_INVALID, "n_batch must be in [1, max_batch of the descriptor]");
         if (conserving(h) && (rc = check_cons_q(h, Q_dev))) return rc;
         h->be.begin_eval();
-        if (h->g64 || h->g32) {      // size-generic path: all members through every launch of the fused sequence, else one by one
-            bool together = false;
-            h->with([&](auto& p) { together = p.batch_together(); });
-            if (together) h->with([&](auto& p) { p.gain_partial(f_dev, n_batch); p.finish(Q_dev, f_dev, with_loss != 0, n_batch); });
-            else
-                for (int i = 0; i < n_batch; ++i)
-                    h->with([&](auto& p) { p.gain_partial(f_dev + (size_t)i * h->G); p.finish(Q_dev + (size_t)i * h->G, f_dev + (size_t)i * h->G, with_loss != 0); });
-        } else {
-            h->with([&](auto& p) {
-                // a batch of one on a single-evaluation N = 16 handle takes the same whole-direction kernels as bfsm_collide
-                if (p.small_path(n_batch)) { p.collide_small(Q_dev, f_dev, with_loss != 0); return; }
-                const bool fu = p.fuse_reduce(); p.gain_partial(f_dev, n_batch, !fu); p.finish(Q_dev, f_dev, with_loss != 0, n_batch, fu);
-            });
-        }
+        h->with([&](auto& p) { bfsm::collide(p, Q_dev, f_dev, n_batch, with_loss != 0, p.fuse_reduce()); });
         if (conserving(h)) h->cons->apply(Q_dev, n_batch);
         return leave(h, "bfsm_collide_batch");
     )
@@ -837,13 +759,7 @@ int bfsm_collide_partial_async(bfsm_handle h, double* Q_dev, const double* f_dev
         if (!f_dev || !Q_dev) return fail(h, BFSM_ERR_INVALID, "null f or Q");
         if (conserving(h) && (rc = check_cons_q(h, Q_dev))) return rc;
         h->be.begin_eval();
-        // gain kernels, then the tail; with few slabs the reduce is fused into its first kernel (qhat is not written then)
-        h->with([&](auto& p) {
-            if (p.small_path(1)) { p.collide_small(Q_dev, f_dev, with_loss != 0); return; }   // N = 16: whole-direction kernels
-            const bool fu = p.fuse_reduce();
-            p.gain_partial(f_dev, 1, !fu);
-            p.finish(Q_dev, f_dev, with_loss != 0, 1, fu);
-        });
+        h->with([&](auto& p) { bfsm::collide(p, Q_dev, f_dev, 1, with_loss != 0, p.fuse_reduce()); });
         if (conserving(h)) h->cons->apply(Q_dev, 1);
         return leave(h, "bfsm_collide_partial");
     )
@@ -914,13 +830,7 @@ int bfsm_collide_split_batch_partial_async(bfsm_handle h, double* Qgain_dev, dou
         if (ranges_overlap(Qgain_dev, f_dev, n) || (nu_dev && (ranges_overlap(nu_dev, f_dev, n) || ranges_overlap(nu_dev, Qgain_dev, n))))
             return fail(h, BFSM_ERR_INVALID, "Qgain and nu must not overlap each other or f");
         h->be.begin_eval();
-        double* nu = with_loss ? nu_dev : nullptr;
-        for_batch(h, n_batch, [&](auto& p, int i0, int nb) {
-            const size_t o = (size_t)i0 * h->G;
-            const bool fu = p.fuse_reduce();
-            p.gain_partial(f_dev + o, nb, !fu);
-            p.finish(Qgain_dev + o, nullptr, with_loss != 0, nb, fu, nullptr, nu ? nu + o : nullptr);
-        });
+        h->with([&](auto& p) { bfsm::collide_split(p, Qgain_dev, nu_dev, f_dev, n_batch, with_loss != 0, p.fuse_reduce()); });
         return leave(h, "bfsm_collide_split");
     )
 }
@@ -973,7 +883,7 @@ int bfsm_loss_rate_async(bfsm_handle h, double* nu_dev, const double* f_dev, int
             return fail(h, BFSM_ERR_INVALID, "n_batch must be in [1, max_batch of the descriptor]");
         if (ranges_overlap(nu_dev, f_dev, (size_t)n_batch * h->G)) return fail(h, BFSM_ERR_INVALID, "nu must not overlap f");
         h->be.begin_eval();
-        for_batch(h, n_batch, [&](auto& p, int i0, int nb) { p.loss_rate(nu_dev + (size_t)i0 * h->G, f_dev + (size_t)i0 * h->G, nb); });
+        h->with([&](auto& p) { bfsm::loss_rate(p, nu_dev, f_dev, n_batch); });
         return leave(h, "bfsm_loss_rate");
     )
 }

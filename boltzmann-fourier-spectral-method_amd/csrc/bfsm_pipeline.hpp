@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bfsm.h"
@@ -285,6 +286,70 @@ constexpr bool is_line_kind(K k) {
            k == K::NyqRows || k == K::GainLineAccH;
 }
 
+// Threads and dynamic LDS bytes of a launch of kernel `kind`
+template <K kind, int N>
+constexpr int kernel_threads() {
+    if (kind == K::GainInv && pair_tile<N>()) return pair_threads<N>();      // two tiles side by side (N = 32)
+    return kind == K::Reduce ? 256 : (is_line_kind(kind) ? Wg<N>::LINE_THREADS : Wg<N>::THREADS);
+}
+template <K kind, int N, typename T>
+constexpr size_t kernel_lds_bytes() {
+    if (kind == K::GainInv && pair_tile<N>()) return pair_lds_bytes<N, T>();
+    if (kind == K::GainInv && ka_xlane<N, T>()) return ka_xlane_lds_bytes<N, T>();
+    if (kind == K::GainFwd) return kc_lds_bytes<N, T>();
+    if (kind == K::GainInvNyq) return gain_inv_lds_bytes<N, T>();
+    return kind == K::Reduce ? 0 : (is_line_kind(kind) ? line_lds_bytes<N, T>() : tile_lds_bytes<N, T>());
+}
+template <SK kind, typename T>
+constexpr size_t small_kernel_lds_bytes() { return kind == SK::Reduce ? 256 * sizeof(double) : small_lds_bytes<T>(); }
+
+// The body of kernel `kind` on one workgroup (prm: its parameters, ctx: the execution context): the one table from kernel
+// identifiers to the bodies of bfsm_core.hpp, expanded inside namespace bfsm by the __global__ wrappers of bfsm_hip.hip and
+// by the emulator's backend.  A macro, not a function: one more inlined frame between a __global__ wrapper and the body
+// reorders the wrapper's stack slots, the optimiser then takes another path through several kernels, and the asm("+s")
+// operands of DevCtx no longer all stay in SGPRs (K::GainInv, N = 48, fp64, bilinear stops compiling).
+#define BFSM_RUN_BODY(kind, N, T, prm, ctx)                                                                                  \
+    if constexpr (kind == K::TileFwdReal) body_tile_fwd_real<N, T>(prm, ctx);                                                \
+    else if constexpr (kind == K::LineFwd) body_line<N, -1, T>(prm, ctx);                                                    \
+    else if constexpr (kind == K::LineInv) body_line<N, +1, T>(prm, ctx);                                                    \
+    else if constexpr (kind == K::TileFwd) body_tile_c2c<N, -1, T>(prm, ctx);                                                \
+    else if constexpr (kind == K::TileInv) body_tile_c2c<N, +1, T>(prm, ctx);                                                \
+    else if constexpr (kind == K::GainInv && pair_tile<N>()) body_gain_inv_pair<N, T>(prm, ctx);                             \
+    else if constexpr (kind == K::GainInv) body_gain_inv<N, T>(prm, ctx);                                                    \
+    else if constexpr (kind == K::GainLine) body_gain_line<N, T>(prm, ctx);                                                  \
+    else if constexpr (kind == K::GainFwd) body_gain_fwd<N, T>(prm, ctx);                                                    \
+    else if constexpr (kind == K::Reduce) body_reduce<N, T>(prm, ctx);                                                       \
+    else if constexpr (kind == K::TailInv) body_tail_inv<N, T>(prm, ctx);                                                    \
+    else if constexpr (kind == K::TailLine) body_tail_line<N, T>(prm, ctx);                                                  \
+    else if constexpr (kind == K::GainLineAcc) body_gain_line_acc<N, T>(prm, ctx);                                           \
+    else if constexpr (kind == K::NyqRows) body_nyq_rows<N, T>(prm, ctx);                                                    \
+    else if constexpr (kind == K::GainLineAccH) body_gain_line_acc_h<N, T>(prm, ctx);                                        \
+    else if constexpr (kind == K::GainInvNyq) {          /* only launched where nyq_rides_along<N>() */                      \
+        if constexpr (nyq_rides_along<N>()) body_gain_inv_nyq<N, T>(prm, ctx);                                               \
+    } else if constexpr (kind == K::GainInvTwo) {          /* only launched on ab_interleaved geometries (Hermitian mode) */ \
+        if constexpr (ab_interleaved<N, T>()) body_gain_inv<N, T, false>(prm, ctx);                                          \
+    }
+#define BFSM_RUN_SMALL_BODY(kind, T, prm, ctx)                             \
+    if constexpr (kind == SK::Gain) body_small_gain<T>(prm, ctx);          \
+    else if constexpr (kind == SK::Reduce) body_small_reduce<T>(prm, ctx);
+
+// fn(std::integral_constant<int, N>{}) for the cube size N of the fused pipeline (fused_grid); false: not one of them
+template <class F>
+bool for_fused_n(int N, F&& fn) {
+    switch (N) {
+        case 16: fn(std::integral_constant<int, 16>{}); return true;
+        case 24: fn(std::integral_constant<int, 24>{}); return true;
+        case 32: fn(std::integral_constant<int, 32>{}); return true;
+        case 40: fn(std::integral_constant<int, 40>{}); return true;
+        case 48: fn(std::integral_constant<int, 48>{}); return true;
+        case 80: fn(std::integral_constant<int, 80>{}); return true;     // (80 before 64: the order the kernels have in the
+        case 64: fn(std::integral_constant<int, 64>{}); return true;     // code object, which follows the instantiations here)
+        case 96: fn(std::integral_constant<int, 96>{}); return true;
+        case 128: fn(std::integral_constant<int, 128>{}); return true;
+        default: return false;
+    }
+}
+
 // Device-resident state of one handle.  `Backend` supplies:
 //   void* alloc(size_t), void release(void*), void upload(void* dst, const void* src, size_t), void zero(void*, size_t)
 //   template <K kind, typename T, class P> void launch(int grid_x, int grid_y, int grid_z, const P& params, int N)
@@ -295,7 +360,7 @@ struct Pipeline {
     Backend* be = nullptr;
     // device buffers
     cx<T>* fhat = nullptr;
-    cx<T>* tg = nullptr;
+    cx<T>* tg = nullptr;          // the tail's gain and loss arrays: one block [2][max_batch G], tl = tg + max_batch G
     cx<T>* tl = nullptr;
     cx<T>* qhat = nullptr;
     cx<T>* a1 = nullptr;
@@ -321,11 +386,17 @@ struct Pipeline {
     T* small_part = nullptr;      // [small_wgs + 1][G] real partial results
     int small_wgs = 0, small_per = 0;
 
+    std::vector<void*> owned;     // every device allocation of this pipeline: what destroy() releases
+
+    template <typename U>
+    bool dev_alloc(U*& dst, size_t n) {
+        dst = (U*)be->alloc(n * sizeof(U));
+        if (dst) owned.push_back(dst);
+        return dst != nullptr;
+    }
     template <typename U>
     bool dev_copy(U*& dst, const std::vector<U>& src) {
-        const size_t bytes = (src.empty() ? 1 : src.size()) * sizeof(U);
-        dst = (U*)be->alloc(bytes);
-        if (!dst) return false;
+        if (!dev_alloc(dst, src.empty() ? 1 : src.size())) return false;
         if (!src.empty()) be->upload(dst, src.data(), src.size() * sizeof(U));
         return true;
     }
@@ -353,30 +424,30 @@ struct Pipeline {
         const size_t nslab = slab_count ? slab_count : 1;
         bool ok = true;
         // at least two spectra: the bilinear form Q(g,f) keeps g_hat and f_hat (collide_bilinear)
-        ok = ok && (fhat = (cx<T>*)be->alloc((nb > 2 ? nb : 2) * G * sizeof(cx<T>)));
-        ok = ok && (tg = (cx<T>*)be->alloc(nb * G * sizeof(cx<T>)));
-        ok = ok && (tl = (cx<T>*)be->alloc(nb * G * sizeof(cx<T>)));
-        ok = ok && (qhat = (cx<T>*)be->alloc(nb * G * sizeof(cx<T>)));
+        ok = ok && dev_alloc(fhat, (nb > 2 ? nb : 2) * G);
+        ok = ok && dev_alloc(tg, 2 * nb * G);
+        if (ok) tl = tg + nb * G;
+        ok = ok && dev_alloc(qhat, nb * G);
         a_planes = plan.hermitian ? plan.N / 2 + 1 : plan.N;
         const size_t Gp = (size_t)a_planes * plan.N * plan.N;       // elements of A1' / A2' per direction
         if (interleaved()) {
             // {A1', A2'} side by side in a1; a KB that writes every P'_d needs a buffer of its own for it (see ab_interleaved)
-            ok = ok && (a1 = (cx<T>*)be->alloc(2 * nb * cap * Gp * sizeof(cx<T>)));
-            if (!segment_sums()) ok = ok && (pp = (cx<T>*)be->alloc(nb * cap * G * sizeof(cx<T>)));
+            ok = ok && dev_alloc(a1, 2 * nb * cap * Gp);
+            if (!segment_sums()) ok = ok && dev_alloc(pp, nb * cap * G);
         } else {
-            ok = ok && (a1 = (cx<T>*)be->alloc(nb * cap * Gp * sizeof(cx<T>)));
-            ok = ok && (a2 = (cx<T>*)be->alloc(nb * cap * Gp * sizeof(cx<T>)));
+            ok = ok && dev_alloc(a1, nb * cap * Gp);
+            ok = ok && dev_alloc(a2, nb * cap * Gp);
             pp = a1;
         }
-        if (plan.hermitian) ok = ok && (rnyq = (cx<T>*)be->alloc(nb * cap * r_per_dir() * sizeof(cx<T>)));
-        ok = ok && (slab = (cx<T>*)be->alloc(nb * nslab * G * sizeof(cx<T>)));
+        if (plan.hermitian) ok = ok && dev_alloc(rnyq, nb * cap * r_per_dir());
+        ok = ok && dev_alloc(slab, nb * nslab * G);
         ok = ok && dev_copy(tw, t.tw) && dev_copy(phx, t.phx) && dev_copy(phy, t.phy) && dev_copy(phz, t.phz);
         ok = ok && dev_copy(dirw, t.dirw) && dev_copy(beta1, t.beta1) && dev_copy(beta2, t.beta2) && dev_copy(segs, plan.segs);
         if (ok && segment_sums()) {
             std::vector<Segment> unit(plan.segs.size());
             for (size_t i = 0; i < unit.size(); ++i) unit[i] = Segment{(int)i, 1, plan.segs[i].r, 0};
             std::vector<T> one(unit.size() ? unit.size() : 1, (T)1);
-            ok = ok && (pseg = (cx<T>*)be->alloc(nb * nslab * G * sizeof(cx<T>)));
+            ok = ok && dev_alloc(pseg, nb * nslab * G);
             ok = ok && dev_copy(segs_unit, unit) && dev_copy(ones, one);
         }
         if (ok && plan.N == SMALL_N && !(d.flags & BFSM_FLAG_NO_SMALL_PATH) && plan.n_dirs() > 0 && max_batch == 1) {
@@ -386,7 +457,7 @@ struct Pipeline {
             const long long wg = nd < 256 ? nd : 256;
             small_per = (int)((nd + wg - 1) / wg);
             small_wgs = (int)((nd + small_per - 1) / small_per);
-            ok = ok && (small_part = (T*)be->alloc((size_t)(small_wgs + 1) * G * sizeof(T)));
+            ok = ok && dev_alloc(small_part, (size_t)(small_wgs + 1) * G);
         }
         if (!ok) { err = "device allocation failed"; return BFSM_ERR_NOMEM; }
         return BFSM_OK;
@@ -412,15 +483,8 @@ struct Pipeline {
 
     void destroy() {
         if (!be) return;
-        if (small_part) { be->release(small_part); small_part = nullptr; }
-        if (pp && pp != a1) be->release(pp);
-        pp = nullptr;
-        void* ptrs[] = {fhat, tg, tl, qhat, a1, a2, slab, tw, phx, phy, phz, dirw, beta1, beta2, segs, pseg, segs_unit, ones, rnyq};
-        for (void* p : ptrs) if (p) be->release(p);
-        fhat = tg = tl = qhat = a1 = a2 = slab = tw = phx = phy = phz = nullptr;
-        dirw = beta1 = beta2 = nullptr;
-        segs = nullptr;
-        pseg = nullptr; segs_unit = nullptr; ones = nullptr; rnyq = nullptr;
+        for (void* p : owned) be->release(p);
+        *this = Pipeline();       // no pointer to released memory survives
     }
 
     double cbytes() const { return (double)sizeof(cx<T>); }

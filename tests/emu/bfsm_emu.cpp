@@ -2,8 +2,9 @@
 //
 // There is no GPU in the authoring container, so the index algebra of the kernels (who owns which point, LDS
 // exchange addresses, twiddle indices, layouts, chunk/slab bookkeeping) is unit-tested on the CPU by running the
-// SAME bodies (csrc/bfsm_core.hpp) and the SAME plan + launch sequence (csrc/bfsm_pipeline.hpp) with a backend
-// in which every GPU thread is a ucontext coroutine and __syncthreads() is a yield to a round-robin scheduler.
+// SAME bodies (csrc/bfsm_core.hpp), the SAME kernel table and plan (csrc/bfsm_pipeline.hpp) and the SAME launch
+// sequences the library's entry points call (csrc/bfsm_calls.hpp) with a backend in which every GPU thread is a ucontext
+// coroutine and __syncthreads() is a yield to a round-robin scheduler.
 // Nothing here is linked into libbfsm_hip.so; the product has no CPU path.
 #define BFSM_HD inline __attribute__((always_inline))
 #include <ucontext.h>
@@ -19,6 +20,7 @@
 
 #include "../../boltzmann-fourier-spectral-method_amd/csrc/bfsm_pipeline.hpp"
 #include "../../boltzmann-fourier-spectral-method_amd/csrc/bfsm_generic.hpp"
+#include "../../boltzmann-fourier-spectral-method_amd/csrc/bfsm_calls.hpp"
 
 namespace emu {
 
@@ -183,61 +185,36 @@ struct EmuBackend {
     void mark(int, double) {}
     bool failed = false;   // a block ended with threads stuck at mismatched barriers
 
+    // every launch allocates the LDS bytes the library's launch of that kernel asks for (kernel_lds_bytes and its kin)
     template <bfsm::K kind, int N, typename T, class P>
     static void body(void* a, EmuCtx& ctx) {
         using namespace bfsm;
         const P& prm = *static_cast<const P*>(a);
-        if constexpr (kind == K::TileFwdReal) body_tile_fwd_real<N, T>(prm, ctx);
-        else if constexpr (kind == K::LineFwd) body_line<N, -1, T>(prm, ctx);
-        else if constexpr (kind == K::LineInv) body_line<N, +1, T>(prm, ctx);
-        else if constexpr (kind == K::TileFwd) body_tile_c2c<N, -1, T>(prm, ctx);
-        else if constexpr (kind == K::TileInv) body_tile_c2c<N, +1, T>(prm, ctx);
-        else if constexpr (kind == K::GainInv && pair_tile<N>()) body_gain_inv_pair<N, T>(prm, ctx);
-        else if constexpr (kind == K::GainInv) body_gain_inv<N, T>(prm, ctx);
-        else if constexpr (kind == K::GainLine) body_gain_line<N, T>(prm, ctx);
-        else if constexpr (kind == K::GainFwd) body_gain_fwd<N, T>(prm, ctx);
-        else if constexpr (kind == K::Reduce) body_reduce<N, T>(prm, ctx);
-        else if constexpr (kind == K::TailInv) body_tail_inv<N, T>(prm, ctx);
-        else if constexpr (kind == K::TailLine) body_tail_line<N, T>(prm, ctx);
-        else if constexpr (kind == K::GainLineAcc) body_gain_line_acc<N, T>(prm, ctx);
-        else if constexpr (kind == K::NyqRows) body_nyq_rows<N, T>(prm, ctx);
-        else if constexpr (kind == K::GainLineAccH) body_gain_line_acc_h<N, T>(prm, ctx);
-        else if constexpr (kind == K::GainInvNyq) {
-            if constexpr (nyq_rides_along<N>()) body_gain_inv_nyq<N, T>(prm, ctx);
-        } else if constexpr (kind == K::GainInvTwo) {
-            if constexpr (ab_interleaved<N, T>()) body_gain_inv<N, T, false>(prm, ctx);
-        }
+        BFSM_RUN_BODY(kind, N, T, prm, ctx)
     }
 
     template <bfsm::K kind, int N, typename T, class P>
     void launch_n(int gx, int gy, int gz, const P& prm) {
-        const bool pair = kind == bfsm::K::GainInv && bfsm::pair_tile<N>();
-        const int threads = pair ? bfsm::pair_threads<N>() : kind == bfsm::K::Reduce ? 256
-                            : (bfsm::is_line_kind(kind) ? bfsm::Wg<N>::LINE_THREADS : bfsm::Wg<N>::THREADS);
-        smem.assign(pair ? bfsm::pair_lds_bytes<N, T>()
-                         : (kind == bfsm::K::GainInv && bfsm::ka_xlane<N, T>()) ? bfsm::ka_xlane_lds_bytes<N, T>()
-                         : kind == bfsm::K::GainFwd ? bfsm::kc_lds_bytes<N, T>()
-                         : kind == bfsm::K::GainInvNyq ? bfsm::gain_inv_lds_bytes<N, T>()
-                         : (bfsm::is_line_kind(kind) ? bfsm::line_lds_bytes<N, T>() : bfsm::tile_lds_bytes<N, T>()), 0xCD);
+        smem.assign(bfsm::kernel_lds_bytes<kind, N, T>(), 0xCD);
         P copy = prm;
         for (int bz = 0; bz < gz; ++bz)
             for (int by = 0; by < gy; ++by)
                 for (int bx = 0; bx < gx; ++bx) {
-                    sched.run_block(threads, bx, by, bz, smem.data(), &body<kind, N, T, P>, &copy, gx, gy);
+                    sched.run_block(bfsm::kernel_threads<kind, N>(), bx, by, bz, smem.data(), &body<kind, N, T, P>, &copy, gx, gy);
                     if (sched.deadlock) failed = true;
                 }
     }
 
     template <bfsm::SK kind, typename T, class P>
     static void body_small(void* a, EmuCtx& ctx) {
+        using namespace bfsm;
         const P& prm = *static_cast<const P*>(a);
-        if constexpr (kind == bfsm::SK::Gain) bfsm::body_small_gain<T>(prm, ctx);
-        else if constexpr (kind == bfsm::SK::Reduce) bfsm::body_small_reduce<T>(prm, ctx);
+        BFSM_RUN_SMALL_BODY(kind, T, prm, ctx)
     }
 
     template <bfsm::SK kind, typename T, class P>
     void launch_small(int gx, const P& prm) {
-        smem.assign(bfsm::small_lds_bytes<T>(), 0xCD);
+        smem.assign(bfsm::small_kernel_lds_bytes<kind, T>(), 0xCD);
         P copy = prm;
         for (int bx = 0; bx < gx; ++bx) {
             sched.run_block(bfsm::SMALL_THREADS, bx, 0, 0, smem.data(), &body_small<kind, T, P>, &copy);
@@ -247,18 +224,9 @@ struct EmuBackend {
 
     template <bfsm::GK kind, typename T, class P>
     static void body_gen(void* a, EmuCtx& ctx) {
+        using namespace bfsm;
         const P& prm = *static_cast<const P*>(a);
-        if constexpr (kind == bfsm::GK::Fft) bfsm::body_gen_fft<T, false, bfsm::GEN_C>(prm, ctx);
-    else if constexpr (kind == bfsm::GK::FftBig) bfsm::body_gen_fft<T, true, bfsm::GEN_C>(prm, ctx);
-    else if constexpr (kind == bfsm::GK::Plane) bfsm::body_gen_plane<T>(prm, ctx);
-        else if constexpr (kind == bfsm::GK::Acc) bfsm::body_gen_acc<T>(prm, ctx);
-        else if constexpr (kind == bfsm::GK::Combine) bfsm::body_gen_combine<T>(prm, ctx);
-        else if constexpr (kind == bfsm::GK::Line3) bfsm::body_gen_line3<T, bfsm::GEN_C>(prm, ctx);
-        else if constexpr (kind == bfsm::GK::PlaneAcc) bfsm::body_gen_plane_acc<T>(prm, ctx);
-        else if constexpr (kind == bfsm::GK::PlanePair) bfsm::body_gen_plane_pair<T>(prm, ctx);
-        else if constexpr (kind == bfsm::GK::Fft8) bfsm::body_gen_fft<T, false, 8>(prm, ctx);
-        else if constexpr (kind == bfsm::GK::FftBig8) bfsm::body_gen_fft<T, true, 8>(prm, ctx);
-        else if constexpr (kind == bfsm::GK::Line38) bfsm::body_gen_line3<T, 8>(prm, ctx);
+        BFSM_RUN_GEN_BODY(kind, T, prm, ctx)
     }
 
     template <bfsm::GK kind, typename T, class P>
@@ -274,92 +242,56 @@ struct EmuBackend {
 
     template <bfsm::K kind, typename T, class P>
     void launch(int gx, int gy, int gz, const P& prm, int N) {
-        switch (N) {
-            case 16: launch_n<kind, 16, T>(gx, gy, gz, prm); break;
-            case 24: launch_n<kind, 24, T>(gx, gy, gz, prm); break;
-            case 32: launch_n<kind, 32, T>(gx, gy, gz, prm); break;
-            case 40: launch_n<kind, 40, T>(gx, gy, gz, prm); break;
-            case 48: launch_n<kind, 48, T>(gx, gy, gz, prm); break;
-            case 80: launch_n<kind, 80, T>(gx, gy, gz, prm); break;
-            case 64: launch_n<kind, 64, T>(gx, gy, gz, prm); break;
-            case 96: launch_n<kind, 96, T>(gx, gy, gz, prm); break;
-            case 128: launch_n<kind, 128, T>(gx, gy, gz, prm); break;
-            default: break;
-        }
+        bfsm::for_fused_n(N, [&](auto n) { launch_n<kind, decltype(n)::value, T>(gx, gy, gz, prm); });
     }
 };
 
-// size-generic path (bfsm_generic.hpp): same sequence as the library's entry points for such grids
-template <typename T>
-int collide_gen_t(const bfsm_desc* d, const double* f, double* Q, double* qhat_out, int nb, bool with_loss) {
-    EmuBackend be;
-    bfsm::GenericPipeline<T, EmuBackend> p;
-    std::string err;
-    int rc = p.init(*d, &be, err);
-    if (rc) return rc;
-    if (nb < 1 || nb > p.max_batch) return BFSM_ERR_INVALID;
-    if (p.batch_together()) {                 // as bfsm_collide_batch_partial_async: all members through every launch
-        p.gain_partial(f, nb);
-        if (qhat_out)
-            for (size_t k = 0; k < p.G * (size_t)nb; ++k) { qhat_out[2 * k] = (double)p.qhat[k].x; qhat_out[2 * k + 1] = (double)p.qhat[k].y; }
-        if (Q) p.finish(Q, f, with_loss, nb);
+// The frame of every emulated entry point: a pipeline of the type that serves the descriptor (as bfsm_create chooses it),
+// initialised on a fresh backend, handed to fn, destroyed.  n_batch is checked against the handle's max_batch.
+template <class F>
+int with_pipeline(const bfsm_desc* d, int n_batch, F&& fn) {
+    auto run = [&](auto p) {
+        EmuBackend be;
+        std::string err;
+        int rc = p.init(*d, &be, err);
+        if (!rc && (n_batch < 1 || n_batch > p.max_batch)) rc = BFSM_ERR_INVALID;
+        if (!rc) fn(p);
         p.destroy();
-        return be.failed ? 99 : 0;
-    }
-    for (int i = 0; i < nb; ++i) {
-        p.gain_partial(f + (size_t)i * p.G);
-        if (qhat_out)
-            for (size_t k = 0; k < p.G; ++k) { qhat_out[2 * ((size_t)i * p.G + k)] = (double)p.qhat[k].x; qhat_out[2 * ((size_t)i * p.G + k) + 1] = (double)p.qhat[k].y; }
-        if (Q) p.finish(Q + (size_t)i * p.G, f + (size_t)i * p.G, with_loss);
-    }
-    p.destroy();
-    return be.failed ? 99 : 0;
+        return rc ? rc : (be.failed ? 99 : 0);
+    };
+    if (bfsm::fused_grid(*d))
+        return d->precision == BFSM_F64 ? run(bfsm::Pipeline<double, EmuBackend>()) : run(bfsm::Pipeline<float, EmuBackend>());
+    return d->precision == BFSM_F64 ? run(bfsm::GenericPipeline<double, EmuBackend>()) : run(bfsm::GenericPipeline<float, EmuBackend>());
 }
 
-template <typename T>
-int collide_t(const bfsm_desc* d, const double* f, double* Q, double* qhat_out, int nb, bool with_loss = true) {
-    if (!bfsm::fused_grid(*d)) return collide_gen_t<T>(d, f, Q, qhat_out, nb, with_loss);
-    EmuBackend be;
-    bfsm::Pipeline<T, EmuBackend> p;
-    std::string err;
-    int rc = p.init(*d, &be, err);
-    if (rc) return rc;
-    if (nb < 1 || nb > p.max_batch) return BFSM_ERR_INVALID;
-    // qhat requested: the two-call sequence (bfsm_gain_partial, bfsm_finish); otherwise the fused sequence of
-    // bfsm_collide / bfsm_collide_batch / bfsm_collide_partial_async (slab reduce inside the first tail kernel)
-    const bool fused = qhat_out == nullptr;   // (the library additionally fuses only shards with few slabs)
-    if (fused && Q && p.small_path(nb)) {     // N = 16: the whole-direction kernels, as bfsm_collide_partial_async
-        p.collide_small(Q, f, with_loss);
-        p.destroy();
-        return be.failed ? 99 : 0;
-    }
-    p.gain_partial(f, nb, !fused);
-    if (qhat_out) {
-        const size_t G = p.plan.G() * (size_t)nb;
-        for (size_t i = 0; i < G; ++i) { qhat_out[2 * i] = (double)p.qhat[i].x; qhat_out[2 * i + 1] = (double)p.qhat[i].y; }
-    }
-    if (Q) p.finish(Q, f, with_loss, nb, fused);
-    p.destroy();
-    return be.failed ? 99 : 0;
+// qhat_out requested: the two calls bfsm_gain_partial, bfsm_finish per group of members, qhat copied out in between.
+// Otherwise the sequence of bfsm_collide / bfsm_collide_batch / bfsm_collide_partial_async.
+inline int collide(const bfsm_desc* d, const double* f, double* Q, double* qhat_out, int nb, bool with_loss = true) {
+    return with_pipeline(d, nb, [&](auto& p) {
+        // fuse = true is a test override of the library's rule (p.fuse_reduce()): the fused tail also runs above 8 slabs here
+        if (!qhat_out) { bfsm::collide(p, Q, f, nb, with_loss, true); return; }
+        const size_t G = p.plan.G();
+        bfsm::for_batch(p, nb, [&](int i0, int n) {
+            const size_t o = (size_t)i0 * G;
+            p.gain_partial(f + o, n);
+            for (size_t k = 0; k < G * (size_t)n; ++k) { qhat_out[2 * (o + k)] = (double)p.qhat[k].x; qhat_out[2 * (o + k) + 1] = (double)p.qhat[k].y; }
+            if (Q) p.finish(Q + o, f + o, with_loss, n);
+        });
+    });
 }
 
 // Tail only: f_hat is recomputed (gain of an empty shard), qhat_in replaces the handle's buffer (what the all-reduce
 // leaves there on a multi-GPU node), then bfsm_finish.
-template <typename T>
-int finish_t(const bfsm_desc* d, const double* f, const double* qhat_in, double* Q, int with_loss) {
-    EmuBackend be;
-    bfsm::Pipeline<T, EmuBackend> p;
-    std::string err;
+inline int finish(const bfsm_desc* d, const double* f, const double* qhat_in, double* Q, int with_loss) {
     bfsm_desc e = *d;
     e.dir_begin = e.dir_end = 1;   // empty shard: F1 + zero gain
-    int rc = p.init(e, &be, err);
-    if (rc) return rc;
-    p.gain_partial(f);
-    const size_t G = p.plan.G();
-    for (size_t i = 0; i < G; ++i) p.qhat[i] = {(T)qhat_in[2 * i], (T)qhat_in[2 * i + 1]};
-    p.finish(Q, f, with_loss != 0);
-    p.destroy();
-    return be.failed ? 99 : 0;
+    return with_pipeline(&e, 1, [&](auto& p) {
+        using T = decltype(p.qhat->x);
+        p.gain_partial(f);
+        const size_t G = p.plan.G();
+        for (size_t i = 0; i < G; ++i) p.qhat[i] = {(T)qhat_in[2 * i], (T)qhat_in[2 * i + 1]};
+        p.finish(Q, f, with_loss != 0);
+    });
 }
 
 template <typename T>
@@ -464,14 +396,11 @@ int gen_routes_t(const bfsm_desc* d, int op, int nb, std::vector<RouteRec>& out,
     switch (op) {
         case 0:     // bfsm_collide_partial_async, with_loss = 1 (bfsm_collide on a full handle)
         case 2:     // ... with_loss = 0
-            p.gain_partial(f, 1, !p.fuse_reduce());
-            p.finish(Q, f, op == 0, 1, p.fuse_reduce());
+            bfsm::collide(p, Q, f, 1, op == 0, p.fuse_reduce());
             break;
         case 1:     // bfsm_collide_batch_partial_async, with_loss = 1
             if (nb < 1 || nb > p.max_batch) { p.destroy(); return BFSM_ERR_INVALID; }
-            if (p.batch_together()) { p.gain_partial(f, nb); p.finish(Q, f, true, nb); }
-            else
-                for (int i = 0; i < nb; ++i) { p.gain_partial(f + (size_t)i * p.G); p.finish(Q + (size_t)i * p.G, f + (size_t)i * p.G, true); }
+            bfsm::collide(p, Q, f, nb, true, p.fuse_reduce());
             break;
         case 3:     // bfsm_collide_bilinear_partial_async, with_loss = 1, g != f
             p.collide_bilinear(Q, g, f, true);
@@ -533,8 +462,7 @@ int bfsm_emu_collide_batch(const bfsm_desc* d, const double* f, double* Q, doubl
     std::string err;
     int rc = bfsm::validate_desc(*d, err);
     if (rc) return rc;
-    return d->precision == BFSM_F64 ? emu::collide_t<double>(d, f, Q, qhat_out, n_batch)
-                                    : emu::collide_t<float>(d, f, Q, qhat_out, n_batch);
+    return emu::collide(d, f, Q, qhat_out, n_batch);
 }
 
 // Emulated bfsm_collide_partial_async on a direction shard: fused gain + tail, with or without the loss term.
@@ -542,8 +470,7 @@ int bfsm_emu_collide_partial(const bfsm_desc* d, const double* f, double* Q, int
     std::string err;
     int rc = bfsm::validate_desc(*d, err);
     if (rc) return rc;
-    return d->precision == BFSM_F64 ? emu::collide_t<double>(d, f, Q, nullptr, 1, with_loss != 0)
-                                    : emu::collide_t<float>(d, f, Q, nullptr, 1, with_loss != 0);
+    return emu::collide(d, f, Q, nullptr, 1, with_loss != 0);
 }
 
 int bfsm_emu_collide(const bfsm_desc* d, const double* f, double* Q, double* qhat_out) {
@@ -555,12 +482,12 @@ int bfsm_emu_finish(const bfsm_desc* d, const double* f, const double* qhat_in, 
     std::string err;
     int rc = bfsm::validate_desc(*d, err);
     if (rc) return rc;
-    return d->precision == BFSM_F64 ? emu::finish_t<double>(d, f, qhat_in, Q, with_loss) : emu::finish_t<float>(d, f, qhat_in, Q, with_loss);
+    return emu::finish(d, f, qhat_in, Q, with_loss);
 }
 
 // Emulated bfsm_fft3d; data = batch*G interleaved complex doubles (narrowed to float when precision == 32).
 int bfsm_emu_fft3d(int N, int precision, double* data, int batch, int sign) {
-    if (N != 16 && N != 24 && N != 32 && N != 40 && N != 48 && N != 64 && N != 80 && N != 96 && N != 128) return BFSM_ERR_UNSUPPORTED;
+    if (!bfsm::for_fused_n(N, [](auto) {})) return BFSM_ERR_UNSUPPORTED;
     if (precision == BFSM_F64) return emu::fft3d_t<double>(N, data, batch, sign);
     return emu::fft3d_t<float>(N, data, batch, sign);
 }

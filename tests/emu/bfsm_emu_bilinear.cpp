@@ -4,22 +4,6 @@
 // library by tests/test_emu_bilinear.py with the flags of tests/emu/Makefile.
 #include "bfsm_emu.cpp"
 
-namespace emu {
-
-template <typename T, class Pipe>
-int collide_bilinear_t(const bfsm_desc* d, const double* g, const double* f, double* Q, int with_loss) {
-    EmuBackend be;
-    Pipe p;
-    std::string err;
-    int rc = p.init(*d, &be, err);
-    if (rc) return rc;
-    p.collide_bilinear(Q, g, f, with_loss != 0);
-    p.destroy();
-    return be.failed ? 99 : 0;
-}
-
-}  // namespace emu
-
 extern "C" {
 
 // Emulated bfsm_collide_bilinear_partial_async (with_loss = 1 and all directions: bfsm_collide_bilinear) on host arrays.
@@ -28,11 +12,7 @@ int bfsm_emu_collide_bilinear(const bfsm_desc* d, const double* g, const double*
     int rc = bfsm::validate_desc(*d, err);
     if (rc) return rc;
     if (d->flags & BFSM_FLAG_EXACT_REDUCTIONS) return BFSM_ERR_UNSUPPORTED;
-    if (bfsm::fused_grid(*d))
-        return d->precision == BFSM_F64 ? emu::collide_bilinear_t<double, bfsm::Pipeline<double, emu::EmuBackend>>(d, g, f, Q, with_loss)
-                                        : emu::collide_bilinear_t<float, bfsm::Pipeline<float, emu::EmuBackend>>(d, g, f, Q, with_loss);
-    return d->precision == BFSM_F64 ? emu::collide_bilinear_t<double, bfsm::GenericPipeline<double, emu::EmuBackend>>(d, g, f, Q, with_loss)
-                                    : emu::collide_bilinear_t<float, bfsm::GenericPipeline<float, emu::EmuBackend>>(d, g, f, Q, with_loss);
+    return emu::with_pipeline(d, 1, [&](auto& p) { p.collide_bilinear(Q, g, f, with_loss != 0); });
 }
 
 }  // extern "C"

@@ -10,10 +10,9 @@ namespace emu {
 struct ConsEmuBackend : EmuBackend {
     template <bfsm::CK kind>
     static void body_cons(void* a, EmuCtx& ctx) {
-        const bfsm::ConsParams& prm = *static_cast<const bfsm::ConsParams*>(a);
-        if constexpr (kind == bfsm::CK::Moments) bfsm::body_cons_moments(prm, ctx);
-        else if constexpr (kind == bfsm::CK::Apply) bfsm::body_cons_apply(prm, ctx);
-        else if constexpr (kind == bfsm::CK::Small) bfsm::body_cons_small(prm, ctx);
+        using namespace bfsm;
+        const ConsParams& prm = *static_cast<const ConsParams*>(a);
+        BFSM_RUN_CONS_BODY(kind, prm, ctx)
     }
     template <bfsm::CK kind>
     void launch_cons(int gx, int gy, const bfsm::ConsParams& prm) {

@@ -44,6 +44,10 @@ def _typed(L):
     L.bfsm_emu_gen_routes.restype = ctypes.c_int
     L.bfsm_emu_collide_batch.argtypes = [ctypes.POINTER(capi.Desc), dp, dp, dp, ctypes.c_int]
     L.bfsm_emu_collide_batch.restype = ctypes.c_int
+    L.bfsm_emu_finish.argtypes = [ctypes.POINTER(capi.Desc), dp, dp, dp, ctypes.c_int]
+    L.bfsm_emu_finish.restype = ctypes.c_int
+    L.bfsm_emu_collide_partial.argtypes = [ctypes.POINTER(capi.Desc), dp, dp, ctypes.c_int]
+    L.bfsm_emu_collide_partial.restype = ctypes.c_int
     return L
 
 
@@ -137,11 +141,6 @@ class EmuOperator:
         import torch
         L = lib()
         dp = ctypes.POINTER(ctypes.c_double)
-        if not hasattr(L.bfsm_emu_finish, "_typed"):
-            from bfsm import capi
-            L.bfsm_emu_finish.argtypes = [ctypes.POINTER(capi.Desc), dp, dp, dp, ctypes.c_int]
-            L.bfsm_emu_finish.restype = ctypes.c_int
-            L.bfsm_emu_finish._typed = True
         d, keep = make_desc(self.nv, self.gl, self.sph, *self.args, 64, self.dir_range, self.max_chunk)
         fh = np.ascontiguousarray(f.numpy(), dtype=np.float64)
         qh = np.ascontiguousarray(self.qhat.numpy())
@@ -178,11 +177,6 @@ class EmuOperatorFused(EmuOperator):
         import torch
         L = lib()
         dp = ctypes.POINTER(ctypes.c_double)
-        if not hasattr(L.bfsm_emu_collide_partial, "_typed"):
-            from bfsm import capi
-            L.bfsm_emu_collide_partial.argtypes = [ctypes.POINTER(capi.Desc), dp, dp, ctypes.c_int]
-            L.bfsm_emu_collide_partial.restype = ctypes.c_int
-            L.bfsm_emu_collide_partial._typed = True
         d, keep = make_desc(self.nv, self.gl, self.sph, *self.args, 64, self.dir_range, self.max_chunk)
         fh = np.ascontiguousarray(f.numpy(), dtype=np.float64)
         out = np.empty(self.nv ** 3)
@@ -201,11 +195,6 @@ def collide_partial(f, gl, sph, gamma, b_gamma, L, precision=64, dir_range=(0, 0
     Q = np.empty_like(f)
     dp = ctypes.POINTER(ctypes.c_double)
     L_ = lib()
-    if not hasattr(L_.bfsm_emu_collide_partial, "_typed"):
-        from bfsm import capi
-        L_.bfsm_emu_collide_partial.argtypes = [ctypes.POINTER(capi.Desc), dp, dp, ctypes.c_int]
-        L_.bfsm_emu_collide_partial.restype = ctypes.c_int
-        L_.bfsm_emu_collide_partial._typed = True
     rc = L_.bfsm_emu_collide_partial(ctypes.byref(d), f.ctypes.data_as(dp), Q.ctypes.data_as(dp), 1 if with_loss else 0)
     if rc:
         raise RuntimeError(f"bfsm_emu_collide_partial rc={rc}")

@@ -43,7 +43,7 @@ def lib():
         src = os.path.join(HERE, "emu", "bfsm_emu_conserve.cpp")
         so = os.path.join(HERE, "emu", "libbfsm_emu_conserve.so")
         deps = [src, os.path.join(HERE, "emu", "bfsm_emu.cpp"), os.path.join(ROOT, "include", "bfsm.h")] + \
-               [os.path.join(PKG, "csrc", n) for n in ("bfsm_core.hpp", "bfsm_pipeline.hpp", "bfsm_generic.hpp", "bfsm_conserve.hpp")]
+               [os.path.join(PKG, "csrc", n) for n in ("bfsm_core.hpp", "bfsm_pipeline.hpp", "bfsm_generic.hpp", "bfsm_conserve.hpp", "bfsm_calls.hpp")]
         if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
             tmp = so[:-3] + ".%d.tmp.so" % os.getpid()
             subprocess.check_call([os.environ.get("CXX", "g++")] + _emu_flags() + ["-o", tmp, src])
