@@ -823,6 +823,12 @@ template <int N, typename T> constexpr bool kb_sums_segments() {
     return !(N == 80 || N == 96 || (N == 128 && sizeof(T) == 8));
 #endif
 }
+// Load-ahead schedule of the looping x-line kernel (kb_sum_segment_ahead): the next direction's rows are requested while
+// this direction's transforms run, into the line array that has just died.  Taken only where a same-box A/B against the
+// plain loop showed a gain: N = 64 in double precision.  Every other geometry keeps the plain loop.
+template <int N, typename T> constexpr bool kb_loads_ahead() {
+    return N == 64 && sizeof(T) == 8 && kb_sums_segments<N, T>() && !ab_interleaved<N, T>();
+}
 template <typename T> constexpr bool kb_sums_segments_n(int n) {
     return n == 16 ? kb_sums_segments<16, T>() : n == 24 ? kb_sums_segments<24, T>() : n == 32 ? kb_sums_segments<32, T>()
          : n == 40 ? kb_sums_segments<40, T>() : n == 48 ? kb_sums_segments<48, T>() : n == 64 ? kb_sums_segments<64, T>()
@@ -1445,6 +1451,76 @@ BFSM_HD void body_gain_line_acc(const GainLineAccParams<T>& prm, Ctx& ctx) {
     for (int m = 0; m < E; ++m) ctx.template st_at<UNI>(prm.pseg + obase + (size_t)(u + TT * m) * N * N, pl, acc[m]);
 }
 
+// The E rows of this thread's share of one array of direction d (rows u + T m of the column block) into v.
+template <int N, typename T, class Ctx>
+BFSM_HD void kb_load_rows(cx<T>* v, const cx<T>* arr, size_t base, int u, unsigned pl, Ctx& ctx) {
+    constexpr int E = Wg<N>::E, TT = Wg<N>::T;
+    constexpr bool UNI = Wg<N>::LROW % 64 == 0;
+    const unsigned plo = ctx.lane_off(pl);       // re-materialised per request: keeps the scalar-base addressing form
+#pragma unroll
+    for (int m = 0; m < E; ++m) v[m] = ctx.template ld_stream_at<UNI>(arr + base + (size_t)(u + TT * m) * N * N, plo);
+}
+
+// The load-ahead loop (kb_sum_segment_ahead) runs a direction in two parts, with the request for the next direction's A1'
+// rows between them; the arithmetic is the plain loop's, expression for expression.  First part: x holds A1'_d, y holds
+// A2'_d (its loads may still be in flight); both inverse x transforms and the product, which leaves y dead.
+template <int N, typename T, class Ctx>
+BFSM_HD void kb_inverse_product(Ctx& ctx, cx<T>* x, cx<T>* y, cx<T>* lds, int p, int u, const Twiddles<N, T>& twr) {
+    constexpr int E = Wg<N>::E, NPL = Wg<N>::NPL;
+    fft_line_np<N, NPL, +1, T, false, SYNC_PRE | SYNC_POST>(x, lds, p, u, twr, ctx);
+    fft_line_np<N, NPL, +1, T, false, SYNC_POST>(y, lds, p, u, twr, ctx);
+#pragma unroll
+    for (int m = 0; m < E; ++m) x[m] = cmul(x[m], y[m]);
+}
+// Second part: the direction's own forward x transform and  acc += w * P'_d  (w = dirw_d).
+template <int N, typename T, class Ctx>
+BFSM_HD void kb_forward_sum(Ctx& ctx, cx<T>* x, cx<T>* acc, cx<T>* lds, int p, int u, const Twiddles<N, T>& twr, T w) {
+    constexpr int E = Wg<N>::E, NPL = Wg<N>::NPL;
+    fft_line_np<N, NPL, -1, T, false, 0>(x, lds, p, u, twr, ctx);
+#pragma unroll
+    for (int m = 0; m < E; ++m) {
+        acc[m].x += w * x[m].x;
+        acc[m].y += w * x[m].y;
+    }
+}
+
+// The direction loop of body_gain_line_acc(GainLineSumParams) with the loads one step ahead (kb_loads_ahead).  The plain
+// loop requests the 2 E rows of a direction, waits, and runs three transforms and six barriers with nothing in flight.
+// Here the A1' rows of direction d + 1 are requested behind the product of direction d, when the second array is dead, and
+// fly under the forward transform; its A2' rows are requested at the top of the next trip, behind the sum, and fly under
+// the first inverse transform.  Summation order and every arithmetic expression are the plain loop's: results are
+// bitwise the same.  Registers: the request lands in the registers the product has freed and the compiler renames the
+// arrays from trip to trip (`a = b` costs no move at N = 64 in double precision: 128 VGPRs, no scratch).
+// Nothing is requested past the segment and no request is conditional (a request under `if (d + 1 < end)` keeps both
+// versions of the array alive: 136 VGPRs wanted, 13 spilled): the n - 1 directions that have a successor run in the
+// loop, the last one behind it without a request.  One direction: the loop does not run.
+template <int N, typename T, class Ctx>
+BFSM_HD void kb_sum_segment_ahead(const GainLineSumParams<T>& prm, Ctx& ctx, const Segment& seg, size_t row, unsigned pl, cx<T>* acc,
+                                  cx<T>* lds, int p, int u, const Twiddles<N, T>& twr) {
+    constexpr int E = Wg<N>::E;
+    constexpr size_t dstride = (size_t)N * N * N;
+    if (seg.n <= 0) return;
+    int d = seg.d0;
+    size_t base = (size_t)ctx.bz() * prm.a_bstride + (size_t)d * dstride + row;
+    cx<T> a[E], b[E];
+    kb_load_rows<N, T>(a, prm.a1, base, u, pl, ctx);
+    for (; d < seg.d0 + seg.n - 1; ++d) {
+        kb_load_rows<N, T>(b, prm.a2, base, u, pl, ctx);
+        ctx.sched_fence();                       // all of them issue before the transform of a starts
+        kb_inverse_product<N, T>(ctx, a, b, lds, p, u, twr);
+        base += dstride;
+        const T w = prm.dirw[prm.dir0 + d];      // in front of the request: waiting for it leaves the rows in flight
+        kb_load_rows<N, T>(b, prm.a1, base, u, pl, ctx);
+        kb_forward_sum<N, T>(ctx, a, acc, lds, p, u, twr, w);
+#pragma unroll
+        for (int m = 0; m < E; ++m) a[m] = b[m];
+    }
+    kb_load_rows<N, T>(b, prm.a2, base, u, pl, ctx);
+    ctx.sched_fence();
+    kb_inverse_product<N, T>(ctx, a, b, lds, p, u, twr);
+    kb_forward_sum<N, T>(ctx, a, acc, lds, p, u, twr, prm.dirw[prm.dir0 + d]);
+}
+
 // KB of the faithful mode with the segment sum of KC fused in.  grid = (column blocks, segments of the chunk, batch): the
 // frame of KB' above, the arithmetic of body_gain_line per direction -- both inverse x transforms, the product and the
 // direction's OWN forward x transform -- then  acc += dirw_d * P'_d  in direction order from zero, the sum KC formed from
@@ -1470,6 +1546,8 @@ BFSM_HD void body_gain_line_acc(const GainLineSumParams<T>& prm, Ctx& ctx) {
     cx<T> acc[E];
 #pragma unroll
     for (int m = 0; m < E; ++m) acc[m] = {(T)0, (T)0};
+    if constexpr (kb_loads_ahead<N, T>()) kb_sum_segment_ahead<N, T>(prm, ctx, seg, row, pl, acc, lds, p, u, twr);
+    else
     for (int d = seg.d0; d < seg.d0 + seg.n; ++d) {
         const size_t base = (size_t)ctx.bz() * prm.a_bstride + (size_t)d * N * N * N + row;
         cx<T> a[E], b[E];
