@@ -20,6 +20,10 @@
 //
 // Like bfsm_core.hpp the kernel bodies are templates over an execution context, so tests/emu runs the same code on the
 // host.
+//
+// Host code (GenericPipeline): init decides the route once (choose_route: plane kernel or not, which of the three sequences)
+// and builds its tables with the fused pipeline's builders (bfsm_pipeline.hpp).  Every transform of every entry point is one
+// fft(Step): a pass along an axis, or the (y,z) planes through the plane kernel or two axis passes, as the route has it.
 #pragma once
 #include <cmath>
 #include <string>
@@ -915,12 +919,26 @@ inline bool gen_supported(int nx, int ny, int nz) {
     return true;
 }
 
+// LDS a workgroup may take and still share its CU with a second one / have the CU to itself
+constexpr size_t GEN_LDS_SHARED_CU = (size_t)80 * 1024;
+constexpr size_t GEN_LDS_WHOLE_CU = (size_t)150 * 1024;
+// The sequence a box runs, chosen once in GenericPipeline::init (array moves per direction with / without the plane kernel)
+enum class GenSeq { Fused, Line3, PerAxis };   // 6;  8 / 14;  12 / 18
+struct GenRoute {
+    bool plane = false;       // the (y,z) passes go through the plane kernel
+    bool x_lines = false;     // the x factors are 2, 3, 5: the x-line kernel can serve where its buffers fit
+    GenSeq seq = GenSeq::PerAxis;
+    int moves() const { return seq == GenSeq::Fused ? 6 : (seq == GenSeq::Line3 ? (plane ? 8 : 14) : (plane ? 12 : 18)); }
+};
+constexpr int GEN_YZ = 3;     // "axis" of a step that transforms the (y,z) planes
+
 // Backend additionally supplies:
 //   template <GK kind, typename T, class P> void launch_gen(int grid_x, int grid_y, int threads, size_t lds_bytes, const P&)
 template <typename T, class Backend>
-struct GenericPipeline {
+struct GenericPipeline : DeviceBuffers<Backend> {
+    using DeviceBuffers<Backend>::be; using DeviceBuffers<Backend>::dev_alloc; using DeviceBuffers<Backend>::dev_copy;
     PlanInfo plan;            // N = 0 marks a generic plan; directions, shard and chunks as in the fused pipeline
-    Backend* be = nullptr;
+    GenRoute route;
     int nx = 0, ny = 0, nz = 0;
     size_t G = 0;
     int n_gl = 0;
@@ -943,14 +961,6 @@ struct GenericPipeline {
     T* beta2 = nullptr;
     std::vector<int> radix[3];
 
-    template <typename U>
-    bool dev_copy(U*& dst, const std::vector<U>& src) {
-        dst = (U*)be->alloc((src.empty() ? 1 : src.size()) * sizeof(U));
-        if (!dst) return false;
-        if (!src.empty()) be->upload(dst, src.data(), src.size() * sizeof(U));
-        return true;
-    }
-
     int init(const bfsm_desc& d, Backend* backend, std::string& err) {
         be = backend;
         nx = d.nvx; ny = d.nvy; nz = d.nvz;
@@ -961,17 +971,16 @@ struct GenericPipeline {
             err = "grid size without a kernel";
             return BFSM_ERR_UNSUPPORTED;
         }
-        const long long B = (long long)d.n_gl * d.n_sph;
+        route = choose_route();
         plan = PlanInfo();
-        plan.gen_plane = plane_ok();
-        plan.gen_fused = fused_ok();
-        plan.gen_moves = fused_ok() ? 6 : (line3_ok((size_t)150 * 1024) ? (plane_ok() ? 8 : 14) : (plane_ok() ? 12 : 18));                // exact_reductions / hermitian / antipodal stay false: this path evaluates every
+        plan.gen_plane = route.plane;
+        plan.gen_fused = route.seq == GenSeq::Fused;
+        plan.gen_moves = route.moves();   // exact_reductions / hermitian / antipodal stay false: this path evaluates every
         plan.N = 0;                       // direction whatever the flags say (include/bfsm.h documents them as no-ops here)
         plan.Gtot = G;
         plan.precision = d.precision;
         plan.n_gl = d.n_gl; plan.n_sph = d.n_sph; plan.sph_eff = d.n_sph;
-        if (d.dir_begin == 0 && d.dir_end == 0) { plan.full_begin = 0; plan.full_end = B; }
-        else { plan.full_begin = d.dir_begin; plan.full_end = d.dir_end; }
+        shard_range(d, plan.full_begin, plan.full_end);
         plan.dir_begin = plan.full_begin; plan.dir_end = plan.full_end;
         const long long nd = plan.n_dirs();
         // directions resident at once: bounded by max_chunk (default 256) and by 8 GiB of A1 / A2 scratch
@@ -995,58 +1004,32 @@ struct GenericPipeline {
         const int hx = nx - nx / 2, hy = ny - ny / 2, hz = nz - nz / 2;   // largest |mode| per axis
         n2stride = hx * hx + hy * hy + hz * hz + 1;
         plan.n2stride = n2stride;
-        // tables (host, long double trigonometry like the fused pipeline)
-        const double pi = 3.14159265358979323846;
-        const long double PI_L = 3.141592653589793238462643383279502884L;
-        const double fft_scale = 1.0 / (double)G;
+        // tables: the fused pipeline's (bfsm_pipeline.hpp), one twiddle table and one phase row length per axis
+        const double fft_scale = 1.0 / (double)G, one = 1.0;
         bool ok = true;
-        const int nn[3] = {nx, ny, nz};
-        for (int ax = 0; ax < 3; ++ax) {
-            std::vector<cx<T>> t(nn[ax]);
-            for (int k = 0; k < nn[ax]; ++k) {
-                const long double ang = -2.0L * PI_L * (long double)k / (long double)nn[ax];
-                t[k] = {(T)cosl(ang), (T)sinl(ang)};
-            }
-            ok = ok && dev_copy(tw[ax], t);
-        }
+        for (int ax = 0; ax < 3; ++ax) ok = ok && dev_copy(tw[ax], twiddle_table<T>(axis_len(ax)));
         std::vector<cx<T>> hx_((size_t)nd * nx), hy_((size_t)nd * ny), hz_((size_t)nd * nz);
         std::vector<T> hw((size_t)nd);
         std::vector<int> hr((size_t)nd);
         for (long long i = 0; i < nd; ++i) {
             const long long b = plan.dir_begin + i;
             const int r = (int)(b / d.n_sph), s = (int)(b % d.n_sph);
-            const long double k = -((long double)pi / (2.0L * (long double)d.L)) * (long double)d.gl_nodes[r];
-            auto fill = [&](std::vector<cx<T>>& dst, int n, double sig, double scale) {
-                for (int j = 0; j < n; ++j) {
-                    const int l = j < n / 2 ? j : j - n;
-                    const long double ang = k * (long double)l * (long double)sig;
-                    dst[(size_t)i * n + j] = {(T)(scale * (double)cosl(ang)), (T)(scale * (double)sinl(ang))};
-                }
-            };
-            fill(hx_, nx, d.sx[s], fft_scale);
-            fill(hy_, ny, d.sy[s], 1.0);
-            fill(hz_, nz, d.sz[s], 1.0);
-            hw[(size_t)i] = (T)(fft_scale * d.gl_wts[r] * d.sph_wts[s] * std::pow(d.gl_nodes[r], d.gamma + 2));
+            const long double k = phase_k(d, r);
+            phase_row(&hx_[(size_t)i * nx], nx, k, d.sx[s], &fft_scale);
+            phase_row(&hy_[(size_t)i * ny], ny, k, d.sy[s], &one);
+            phase_row(&hz_[(size_t)i * nz], nz, k, d.sz[s], &one);
+            hw[(size_t)i] = (T)(direction_weight(d, r, s, fft_scale));
             hr[(size_t)i] = r;
         }
-        std::vector<T> b1((size_t)d.n_gl * n2stride), b2v((size_t)n2stride);
-        for (int n2 = 0; n2 < n2stride; ++n2) {
-            const double norm_l = std::sqrt((double)n2);
-            double acc = 0;
-            for (int r = 0; r < d.n_gl; ++r) {
-                b1[(size_t)r * n2stride + n2] = (T)(4 * pi * d.b_gamma * sincc_ref(pi * d.gl_nodes[r] * norm_l / (2 * d.L)));
-                acc += 16 * pi * pi * d.b_gamma * d.gl_wts[r] * std::pow(d.gl_nodes[r], d.gamma + 2) *
-                       sincc_ref(pi * d.gl_nodes[r] * norm_l / d.L);
-            }
-            b2v[n2] = (T)(fft_scale * acc);
-        }
+        std::vector<T> b1, b2v;
+        beta_tables(d, n2stride, fft_scale, b1, b2v);
         ok = ok && dev_copy(phx, hx_) && dev_copy(phy, hy_) && dev_copy(phz, hz_) && dev_copy(dirw, hw) && dev_copy(rdir, hr);
         ok = ok && dev_copy(beta1, b1) && dev_copy(beta2, b2v);
-        ok = ok && (fhat = (cx<T>*)be->alloc((size_t)(mb > 2 ? mb : 2) * G * sizeof(cx<T>)));   // >= 2: Q(g,f) keeps two spectra
-        ok = ok && (qhat = (cx<T>*)be->alloc((size_t)mb * G * sizeof(cx<T>)));
-        ok = ok && (tail = (cx<T>*)be->alloc((size_t)2 * max_batch * G * sizeof(cx<T>)));
-        ok = ok && (a = (cx<T>*)be->alloc((size_t)mb * 2 * chunk * G * sizeof(cx<T>)));
-        if (fused_ok()) {
+        ok = ok && dev_alloc(fhat, (size_t)(mb > 2 ? mb : 2) * G);   // >= 2: Q(g,f) keeps two spectra
+        ok = ok && dev_alloc(qhat, (size_t)mb * G);
+        ok = ok && dev_alloc(tail, (size_t)2 * max_batch * G);
+        ok = ok && dev_alloc(a, (size_t)mb * 2 * chunk * G);
+        if (route.seq == GenSeq::Fused) {
             // the largest launch of gain_chunk_fused: groups_for is not monotone, a shorter last chunk can need more groups
             // than a full one (32 planes: 17 directions make 9 groups of 2, 16 directions 16 groups of 1)
             slab_groups = 1;
@@ -1055,7 +1038,7 @@ struct GenericPipeline {
                 if (g > slab_groups) slab_groups = g;
                 plan.gen_slabs += g;
             }
-            ok = ok && (slab = (cx<T>*)be->alloc((size_t)mb * slab_groups * G * sizeof(cx<T>)));
+            ok = ok && dev_alloc(slab, (size_t)mb * slab_groups * G);
         }
         if (!ok) { err = "device allocation failed"; return BFSM_ERR_NOMEM; }
         return BFSM_OK;
@@ -1063,12 +1046,8 @@ struct GenericPipeline {
 
     void destroy() {
         if (!be) return;
-        void* ptrs[] = {fhat, qhat, tail, a, slab, tw[0], tw[1], tw[2], phx, phy, phz, dirw, rdir, beta1, beta2};
-        for (void* p : ptrs) if (p) be->release(p);
-        fhat = qhat = tail = a = slab = phx = phy = phz = nullptr;
-        tw[0] = tw[1] = tw[2] = nullptr;
-        dirw = beta1 = beta2 = nullptr;
-        rdir = nullptr;
+        this->release_owned();
+        *this = GenericPipeline();    // no pointer to released memory survives
     }
 
     int axis_len(int ax) const { return ax == 0 ? nx : (ax == 1 ? ny : nz); }
@@ -1076,31 +1055,137 @@ struct GenericPipeline {
     bool small_path(int) const { return false; }
     void collide_small(double*, const double*, bool) {}
 
-    // one axis pass over `batch` arrays; member b of in / out sits at + b * in_bstride / + b * out_bstride.  A pass may
-    // run in place: every workgroup reads its whole block of lines into LDS before it stores the same block.
-    void pass(const void* in, const cx<T>* in2, cx<T>* out, int batch, int axis, int sign, int mode, size_t in_bstride,
-              size_t out_bstride, long long dir0 = 0, int mper = 0, size_t in_mstride = 0, size_t out_mstride = 0) {
+    // ---- the route: decided once, in init ----
+    // The plane kernel serves boxes whose plane fits the LDS twice and whose y / z factors are 2, 3, 5.  The fused sequence
+    // (plane kernel straight from f_hat, x-line kernel, plane-accumulate kernel) serves those of them whose x factors are 2, 3,
+    // 5 and whose x-line buffers leave room for two workgroups per CU.  The x-line kernel alone (both inverse x passes, the
+    // product and the forward x pass in one: 4 array moves fewer) also serves boxes whose plane does not fit, as long as its
+    // line buffers fit the CU.  Everything else takes one pass per axis.
+    GenRoute choose_route() const {
+        GenRoute r;
+        bool table[3] = {false, false, false};
+        for (int ax = 0; ax < 3; ++ax) for (int f : radix[ax]) table[ax] = table[ax] || gen_table_radix(f);
+#ifndef BFSM_GEN_NO_PLANE         // A/B builds (tools only): one pass per axis everywhere
+        // ... and leaves room for four workgroups per CU: with bigger planes the one-pass-per-axis kernels (52 KB at most) win
+        // (64 x 48 x 80 in double precision, a 124 KB plane: 0.92 against 1.30 TB/s algorithmic, profiles/r04_generic_ktimes.txt)
+        r.plane = !table[1] && !table[2] && (size_t)2 * ny * (nz + 1) * sizeof(cx<T>) <= (size_t)40 * 1024 && nz <= GEN_THREADS;
+#endif
+#ifndef BFSM_GEN_NO_FUSE          // A/B builds (tools only): the 12-move sequence
+        r.x_lines = !table[0];
+        if (r.plane && r.x_lines && line3_lds() <= GEN_LDS_SHARED_CU) r.seq = GenSeq::Fused;
+        else if (r.x_lines && line3_lds() <= GEN_LDS_WHOLE_CU) r.seq = GenSeq::Line3;
+#endif
+        return r;
+    }
+    bool plane_ok() const { return route.plane; }
+    bool fused_ok() const { return route.seq == GenSeq::Fused; }
+    bool line3_ok(size_t lds_cap) const { return route.x_lines && line3_lds() <= lds_cap; }
+    // batches of distributions go through the fused sequence together (every launch covers all members); the other
+    // sequences take them one after the other
+    bool batch_together() const { return fused_ok(); }
+
+    // ---- LDS bytes and lines per workgroup of each kernel form: what the launches ask for and the route sizes against ----
+    static size_t pass_lds(int n, int C) { return ((size_t)2 * n * (C + 1) + n) * sizeof(cx<T>); }
+    size_t plane_lds() const { return ((size_t)2 * ny * (nz + 1) + ny + nz) * sizeof(cx<T>); }
+    size_t plane_acc_lds() const { return ((size_t)3 * ny * (nz + 1) + ny + nz) * sizeof(cx<T>); }
+    // the x-line kernel: three line buffers, two in the 8-line form (which parks a line in registers instead)
+    size_t line3_lds(int C) const { return ((size_t)(C == 8 ? 2 : 3) * nx * (C + 1) + nx) * sizeof(cx<T>); }
+    size_t line3_lds() const { return line3_lds(line3_lines()); }
+    // 16 lines per workgroup, 8 where 16 would leave one workgroup per CU (two line buffers above 80 KB: n > 147 in
+    // double precision) -- 128-byte instead of 256-byte runs, but three workgroups per CU instead of one
+#ifdef BFSM_GEN_LINES16           // A/B builds (tools only)
+    static constexpr bool LINES16 = true;
+#else
+    static constexpr bool LINES16 = false;
+#endif
+    int pass_lines(int n) const { return !LINES16 && pass_lds(n, GEN_C) > GEN_LDS_SHARED_CU ? 8 : GEN_C; }
+    int line3_lines() const { return !LINES16 && line3_lds(GEN_C) > GEN_LDS_SHARED_CU ? 8 : GEN_C; }
+
+    // ---- one FFT step of a sequence ----
+    // A pass along one axis over `batch` arrays (member b of in / out at + b * in_bstride / + b * out_bstride), or -- axis
+    // GEN_YZ -- both passes of the (y,z) planes: through the plane kernel where the route has it, else as two axis passes
+    // with mark(cat, cat_bytes) between them.  The sign fixes the order of the two (z then y forward, y then z backward, as the
+    // plane kernel has it) unless the step is swapped().  A step may run in place: every workgroup reads its whole block of
+    // lines into LDS before it stores the same block.
+    struct Step {
+        const void* in = nullptr;
+        const cx<T>* in2 = nullptr;                                   // second input of the load-side mode
+        cx<T>* out = nullptr;
+        int batch = 1, sign = -1, axis = GEN_YZ, mode = GEN_PLAIN;    // batch: grid.y; mode: load side of the (first) pass
+        size_t in_bstride = 0, out_bstride = 0;
+        long long dir0 = 0;                                           // GEN_PHASE: shard index of the chunk's first direction
+        int mper = 0; size_t in_mstride = 0, out_mstride = 0;         // member level (GenFftParams::mper) and its strides
+        int cat = -1; double cat_bytes = 0;                           // what a two-pass (y,z) step marks its second launch with
+        bool swap = false;
+        Step& along(int ax) { axis = ax; return *this; }
+        Step& load(int m, const cx<T>* second = nullptr) { mode = m; in2 = second; return *this; }
+        Step& strides(size_t i, size_t o) { in_bstride = i; out_bstride = o; return *this; }
+        Step& from(long long d0) { dir0 = d0; return *this; }
+        Step& members(int per, size_t i, size_t o) { mper = per; in_mstride = i; out_mstride = o; return *this; }
+        Step& marks(int c, double bytes = 0) { cat = c; cat_bytes = bytes; return *this; }
+        Step& swapped() { swap = true; return *this; }
+    };
+    // a (y,z) step over `batch` arrays one after the other (stride G) on both sides
+    Step step(const void* in, cx<T>* out, int batch, int sign) const {
+        Step s;
+        s.in = in; s.out = out; s.batch = batch; s.sign = sign;
+        s.in_bstride = s.out_bstride = G;
+        return s;
+    }
+    void fft(Step s) {
+        // (the plane kernel is named first: the kernels' order in the code object follows the order of use here)
+        if (s.axis == GEN_YZ && route.plane) { plane<GK::Plane>(s); return; }
+        if (s.axis != GEN_YZ) { pass(s); return; }
+        s.axis = ((s.sign < 0) != s.swap) ? 2 : 1;
+        pass(s);
+        be->mark(s.cat, s.cat_bytes);
+        s.in = s.out; s.in2 = nullptr; s.mode = GEN_PLAIN; s.dir0 = 0;      // the second pass: in place, plain
+        s.in_bstride = s.out_bstride; s.in_mstride = s.out_mstride;
+        s.axis = 3 - s.axis;
+        pass(s);
+    }
+
+    // what a step sets in the parameters of every kernel form
+    void fill(GenFftParams<T>& p, const Step& s) const {
+        p.in = s.in; p.in2 = s.in2; p.out = s.out;
+        p.nx = nx; p.ny = ny; p.nz = nz; p.sign = s.sign;
+        p.mode = s.mode; p.phx = phx; p.phy = phy; p.phz = phz; p.dir0 = s.dir0; p.beta2 = beta2;
+        p.in_bstride = s.in_bstride; p.out_bstride = s.out_bstride;
+        p.mper = s.mper; p.in_mstride = s.in_mstride; p.out_mstride = s.out_mstride;
+    }
+    void fill_radix(int axis, int& n_radix, int* r) const {
+        n_radix = (int)radix[axis].size();
+        for (int i = 0; i < n_radix; ++i) r[i] = radix[axis][i];
+    }
+    void pass(const Step& s) {
         GenFftParams<T> p{};
-        p.mper = mper; p.in_mstride = in_mstride; p.out_mstride = out_mstride;
-        p.in = in; p.in2 = in2; p.out = out; p.tw = tw[axis];
-        p.nx = nx; p.ny = ny; p.nz = nz; p.axis = axis; p.sign = sign;
-        const int n = axis_len(axis);
+        fill(p, s);
+        p.axis = s.axis; p.tw = tw[s.axis];
+        const int n = axis_len(s.axis);
         const int ncols = (int)(G / (size_t)n);
-        // 16 lines per workgroup, 8 where 16 would leave one workgroup per CU (two line buffers above 80 KB: n > 147 in
-        // double precision) -- 128-byte instead of 256-byte runs, but three workgroups per CU instead of one
         const int C = pass_lines(n);
         p.C = C;
-        p.n_radix = (int)radix[axis].size();
-        for (int i = 0; i < p.n_radix; ++i) p.radix[i] = radix[axis][i];
-        p.mode = mode; p.phx = phx; p.phy = phy; p.phz = phz; p.dir0 = dir0; p.beta2 = beta2;
-        p.in_bstride = in_bstride; p.out_bstride = out_bstride;
-        const size_t lds = ((size_t)2 * n * (C + 1) + n) * sizeof(cx<T>);
+        fill_radix(s.axis, p.n_radix, p.radix);
+        const size_t lds = pass_lds(n, C);
         bool big = false;
-        for (int r : radix[axis]) big = big || gen_table_radix(r);
-        if (big && C == 8) launch_fft<GK::FftBig8>((ncols + C - 1) / C, batch, lds, p);
-        else if (big) launch_fft<GK::FftBig>((ncols + C - 1) / C, batch, lds, p);
-        else if (C == 8) launch_fft<GK::Fft8>((ncols + C - 1) / C, batch, lds, p);
-        else launch_fft<GK::Fft>((ncols + C - 1) / C, batch, lds, p);
+        for (int r : radix[s.axis]) big = big || gen_table_radix(r);
+        if (big && C == 8) launch_fft<GK::FftBig8>((ncols + C - 1) / C, s.batch, lds, p);
+        else if (big) launch_fft<GK::FftBig>((ncols + C - 1) / C, s.batch, lds, p);
+        else if (C == 8) launch_fft<GK::Fft8>((ncols + C - 1) / C, s.batch, lds, p);
+        else launch_fft<GK::Fft>((ncols + C - 1) / C, s.batch, lds, p);
+    }
+    // kind: GK::Plane, or GK::PlanePair (both signs of a GEN_PHASE producer in one workgroup)
+    template <GK kind>
+    void plane(const Step& s) {
+        GenFftParams<T> p{};
+        fill(p, s);
+        p.axis = 1; p.C = GEN_C;
+        const int first = s.sign < 0 ? 2 : 1, second = 3 - first;          // first / second axis transformed
+        p.tw = tw[first]; p.tw_b = tw[second];
+        fill_radix(first, p.n_radix, p.radix);
+        fill_radix(second, p.n_radix_b, p.radix_b);
+        if (kind == GK::PlanePair) p.beta2 = nullptr;                      // no mode of that kernel reads it
+        launch_fft<kind>(nx, s.batch, plane_lds(), p);
     }
     // a GEN_PHASE producer given a second spectrum (in2) is the bilinear form's: its own instantiation (GenFftBiParams)
     template <GK kind>
@@ -1113,88 +1198,27 @@ struct GenericPipeline {
             be->template launch_gen<kind, T>(gx, gy, GEN_THREADS, lds, p);
         }
     }
-    int pass_lines(int n) const {
-#ifdef BFSM_GEN_LINES16           // A/B builds (tools only)
-        return GEN_C;
-#else
-        return ((size_t)2 * n * (GEN_C + 1) + n) * sizeof(cx<T>) > (size_t)80 * 1024 ? 8 : GEN_C;
-#endif
-    }
-    // ... and the x-line kernel with its three buffers
-    int line3_lines() const {
-#ifdef BFSM_GEN_LINES16
-        return GEN_C;
-#else
-        return ((size_t)3 * nx * (GEN_C + 1) + nx) * sizeof(cx<T>) > (size_t)80 * 1024 ? 8 : GEN_C;
-#endif
-    }
 
-    // the fused (y,z) plane kernel serves boxes whose plane fits the LDS twice and whose y / z factors are 2, 3, 5
-    bool plane_ok() const {
-#ifdef BFSM_GEN_NO_PLANE          // A/B builds (tools only): one pass per axis everywhere
-        return false;
-#else
-        for (int ax = 1; ax <= 2; ++ax) for (int r : radix[ax]) if (gen_table_radix(r)) return false;
-        // ... and leaves room for four workgroups per CU: with bigger planes the one-pass-per-axis kernels (52 KB at most) win
-        // (64 x 48 x 80 in double precision, a 124 KB plane: 0.92 against 1.30 TB/s algorithmic, profiles/r04_generic_ktimes.txt)
-        return (size_t)2 * ny * (nz + 1) * sizeof(cx<T>) <= (size_t)40 * 1024 && nz <= GEN_THREADS;
-#endif
-    }
-    void plane(const void* in, const cx<T>* in2, cx<T>* out, int batch, int sign, int mode, size_t in_bstride, size_t out_bstride,
-               long long dir0 = 0, int mper = 0, size_t in_mstride = 0, size_t out_mstride = 0) {
-        GenFftParams<T> p{};
-        p.mper = mper; p.in_mstride = in_mstride; p.out_mstride = out_mstride;
-        p.in = in; p.in2 = in2; p.out = out;
-        p.nx = nx; p.ny = ny; p.nz = nz; p.axis = 1; p.sign = sign; p.C = GEN_C;
-        const int a = sign < 0 ? 2 : 1, bsec = sign < 0 ? 1 : 2;          // first / second axis transformed
-        p.tw = tw[a]; p.tw_b = tw[bsec];
-        p.n_radix = (int)radix[a].size();
-        for (int i = 0; i < p.n_radix; ++i) p.radix[i] = radix[a][i];
-        p.n_radix_b = (int)radix[bsec].size();
-        for (int i = 0; i < p.n_radix_b; ++i) p.radix_b[i] = radix[bsec][i];
-        p.mode = mode; p.phx = phx; p.phy = phy; p.phz = phz; p.dir0 = dir0; p.beta2 = beta2;
-        p.in_bstride = in_bstride; p.out_bstride = out_bstride;
-        const size_t lds = ((size_t)2 * ny * (nz + 1) + ny + nz) * sizeof(cx<T>);
-        launch_fft<GK::Plane>(nx, batch, lds, p);
-    }
-
-    // The fused sequence (plane kernel straight from f_hat, x-line kernel, plane-accumulate kernel: 6 array moves per
-    // direction) serves the boxes of plane_ok() whose x factors are 2, 3, 5 and whose three x-line buffers leave room for
-    // two workgroups per CU.
-    bool fused_ok() const {
-#ifdef BFSM_GEN_NO_FUSE           // A/B builds (tools only): the 12-move sequence
-        return false;
-#else
-        return plane_ok() && line3_ok((size_t)80 * 1024);
-#endif
-    }
-    // the x-line kernel alone (both inverse x passes, the product and the forward x pass in one: 4 array moves fewer) also
-    // serves boxes whose plane does not fit, as long as its three line buffers fit the CU
-    bool line3_ok(size_t lds_cap) const {
-#ifdef BFSM_GEN_NO_FUSE
-        return false;
-#else
-        for (int r : radix[0]) if (gen_table_radix(r)) return false;
-        return line3_lds() <= lds_cap;
-#endif
-    }
-    // LDS of the x-line kernel: three line buffers, two in the 8-line form (which parks a line in registers instead)
-    size_t line3_lds() const {
-        const int C = line3_lines();
-        return ((size_t)(C == 8 ? 2 : 3) * nx * (C + 1) + nx) * sizeof(cx<T>);
-    }
+    // the x-line kernel over the chunk's A1', A2'
     void line3(const Chunk& c, int nb = 1) {
         GenLineParams<T> kl{};
         kl.a = a; kl.tw = tw[0]; kl.nx = nx; kl.ny = ny; kl.nz = nz;
         kl.n = c.n; kl.mstride = a_mstride();
-        kl.n_radix = (int)radix[0].size();
-        for (int i = 0; i < kl.n_radix; ++i) kl.radix[i] = radix[0][i];
+        fill_radix(0, kl.n_radix, kl.radix);
         const int ncols = ny * nz;
         be->mark(BFSM_K_GAIN_LINE, 3.0 * c.n * nb * (double)G * sizeof(cx<T>));
         const int C = line3_lines();
         const size_t lds = line3_lds();
         if (C == 8) be->template launch_gen<GK::Line38, T>((ncols + C - 1) / C, c.n * nb, GEN_THREADS, lds, kl);
         else be->template launch_gen<GK::Line3, T>((ncols + C - 1) / C, c.n * nb, GEN_THREADS, lds, kl);
+    }
+    // Q_hat (+)= sum over the n arrays p + d * p_bstride (first: = instead of +=), per member of grid.y: weighted by dirw beta1
+    // of the directions dir0 + d, or -- weighted = false -- as they are (the slabs of the fused sequence)
+    void accumulate(const cx<T>* p, size_t p_bstride, int n, long long dir0, bool first, bool weighted, int members = 1,
+                    size_t p_mstride = 0, size_t q_mstride = 0) {
+        GenAccParams<T> ka{p, p_bstride, qhat, nullptr, nullptr, nullptr, dir0, n, n2stride, first ? 1 : 0, nx, ny, nz, p_mstride, q_mstride};
+        if (weighted) { ka.dirw = dirw; ka.rdir = rdir; ka.beta1 = beta1; }
+        be->template launch_gen<GK::Acc, T>((int)((G + GEN_THREADS - 1) / GEN_THREADS), members, GEN_THREADS, 0, ka);
     }
     // groups of directions per x-plane in the plane-accumulate kernel: about 512 workgroups per launch (two per CU; 1024 and
     // 2048 measured 3 % and 7 % slower over the evaluation at 32 x 64 x 16: more slabs to write and to sum)
@@ -1211,9 +1235,6 @@ struct GenericPipeline {
     }
     // elements between the scratch of two batch members
     size_t a_mstride() const { return (size_t)2 * chunk * G; }
-    // batches of distributions go through the fused sequence together (every launch covers all members); the other
-    // sequences take them one after the other
-    bool batch_together() const { return fused_ok(); }
     void gain_chunk_fused(const Chunk& c, bool first, int nb = 1, const cx<T>* fb = nullptr) {
         const double Gc = (double)G * sizeof(cx<T>);
         // A1', A2' = IFFT_yz(alpha f_hat / G), IFFT_yz(conj(alpha) f_hat / G), straight from f_hat (x stays spectral)
@@ -1226,35 +1247,22 @@ struct GenericPipeline {
         // 0.117 -> 0.133 ms there) -- profiles/r04_generic_fused_ab.txt
         constexpr bool PAIR = sizeof(T) == 8;
 #endif
-        if (!PAIR) plane(fhat, fb, a, 2 * c.n * nb, +1, GEN_PHASE, 0, G, c.dir0, 2 * c.n, G, a_mstride());
-        else {
-            GenFftParams<T> ki{};
-            ki.in = fhat; ki.out = a; ki.nx = nx; ki.ny = ny; ki.nz = nz; ki.axis = 1; ki.sign = +1; ki.C = GEN_C; ki.mode = GEN_PHASE;
-            ki.tw = tw[1]; ki.tw_b = tw[2];
-            ki.n_radix = (int)radix[1].size(); ki.n_radix_b = (int)radix[2].size();
-            for (int i = 0; i < ki.n_radix; ++i) ki.radix[i] = radix[1][i];
-            for (int i = 0; i < ki.n_radix_b; ++i) ki.radix_b[i] = radix[2][i];
-            ki.phx = phx; ki.phy = phy; ki.phz = phz; ki.dir0 = c.dir0;
-            ki.mper = c.n; ki.in_mstride = G; ki.out_mstride = a_mstride();
-            ki.in2 = fb;
-            launch_fft<GK::PlanePair>(nx, c.n * nb, ((size_t)2 * ny * (nz + 1) + ny + nz) * sizeof(cx<T>), ki);
-        }
+        if (PAIR) plane<GK::PlanePair>(step(fhat, a, c.n * nb, +1).load(GEN_PHASE, fb).from(c.dir0).strides(0, 0).members(c.n, G, a_mstride()));
+        else plane<GK::Plane>(step(fhat, a, 2 * c.n * nb, +1).load(GEN_PHASE, fb).from(c.dir0).strides(0, G).members(2 * c.n, G, a_mstride()));
         line3(c, nb);
         GenPlaneAccParams<T> kp{};
         const int groups = groups_for(c.n);
         kp.p = a; kp.p_bstride = 2 * G; kp.slab = slab; kp.dirw = dirw; kp.rdir = rdir; kp.beta1 = beta1;
         kp.dir0 = c.dir0; kp.n = c.n; kp.per_group = (c.n + groups - 1) / groups; kp.n2stride = n2stride;
         kp.nx = nx; kp.ny = ny; kp.nz = nz; kp.tw = tw[2]; kp.tw_b = tw[1];
-        kp.n_radix = (int)radix[2].size(); kp.n_radix_b = (int)radix[1].size();
-        for (int i = 0; i < kp.n_radix; ++i) kp.radix[i] = radix[2][i];
-        for (int i = 0; i < kp.n_radix_b; ++i) kp.radix_b[i] = radix[1][i];
+        fill_radix(2, kp.n_radix, kp.radix);
+        fill_radix(1, kp.n_radix_b, kp.radix_b);
         kp.groups = groups; kp.p_mstride = a_mstride();
         be->mark(BFSM_K_GAIN_FWD, (1.0 * c.n + groups) * nb * Gc);
-        be->template launch_gen<GK::PlaneAcc, T>(nx, groups * nb, GEN_THREADS, ((size_t)3 * ny * (nz + 1) + ny + nz) * sizeof(cx<T>), kp);
+        be->template launch_gen<GK::PlaneAcc, T>(nx, groups * nb, GEN_THREADS, plane_acc_lds(), kp);
         // Q_hat (+)= the groups' slabs, fixed order
-        GenAccParams<T> ka{slab, G, qhat, nullptr, nullptr, nullptr, 0, groups, n2stride, first ? 1 : 0, nx, ny, nz, (size_t)groups * G, G};
         be->mark(BFSM_K_REDUCE, (groups + (first ? 1.0 : 2.0)) * nb * Gc);
-        be->template launch_gen<GK::Acc, T>((int)((G + GEN_THREADS - 1) / GEN_THREADS), nb, GEN_THREADS, 0, ka);
+        accumulate(slab, G, groups, 0, first, false, nb, (size_t)groups * G, G);
     }
 
     // f_hat = FFT(f), then the gain term of this shard into qhat   (CUDABoltzmannOperator.cu:131-191)
@@ -1267,14 +1275,10 @@ struct GenericPipeline {
     // out = FFT(f), natural layout
     void spectrum(const double* f_dev, cx<T>* out, int nb) {
         const double Gc = (double)G * sizeof(cx<T>);
-        const bool pl = plane_ok();
         be->mark(BFSM_K_FFT_F, 1.5 * nb * Gc);
-        if (pl) plane(f_dev, nullptr, out, nb, -1, GEN_REAL, G, G);
-        else {
-            pass(f_dev, nullptr, out, nb, 2, -1, GEN_REAL, G, G);
-            be->mark(BFSM_K_FFT_F, 2.0 * nb * Gc); pass(out, nullptr, out, nb, 1, -1, GEN_PLAIN, G, G);
-        }
-        be->mark(BFSM_K_FFT_F, 2.0 * nb * Gc); pass(out, nullptr, out, nb, 0, -1, GEN_PLAIN, G, G);
+        fft(step(f_dev, out, nb, -1).load(GEN_REAL).marks(BFSM_K_FFT_F, 2.0 * nb * Gc));
+        be->mark(BFSM_K_FFT_F, 2.0 * nb * Gc);
+        fft(step(out, out, nb, -1).along(0));
     }
 
     // Bilinear form Q(g,f): as Pipeline::collide_bilinear (g_hat in fhat, f_hat in fhat + G: init reserves two spectra)
@@ -1290,62 +1294,38 @@ struct GenericPipeline {
     // the gain term of this shard from fhat (and fb: the conj(alpha) operand of the bilinear form) into qhat
     void gain_spectra(int nb, const cx<T>* fb) {
         const double Gc = (double)G * sizeof(cx<T>);
-        const bool pl = plane_ok();
         bool first = true;
-        const bool fused = fused_ok(), l3 = line3_ok((size_t)150 * 1024);
         for (const Chunk& c : plan.chunks) {
-            if (fused) { gain_chunk_fused(c, first, nb, fb); first = false; continue; }
-            const int nb2 = 2 * c.n;
-            if (l3) {
-                // the (y,z) passes of the inverse transforms first (phase factors on the load side, straight from f_hat), then
-                // the x-line kernel, then the (y,z) passes of the forward transform: 14 array moves (8 with the plane kernel)
-                be->mark(BFSM_K_GAIN_INV, 2.0 * c.n * Gc);
-                if (pl) plane(fhat, fb, a, nb2, +1, GEN_PHASE, 0, G, c.dir0);
-                else {
-                    pass(fhat, fb, a, nb2, 2, +1, GEN_PHASE, 0, G, c.dir0);
-                    be->mark(BFSM_K_GAIN_INV, 0); pass(a, nullptr, a, nb2, 1, +1, GEN_PLAIN, G, G);
-                }
+            if (route.seq == GenSeq::Fused) { gain_chunk_fused(c, first, nb, fb); first = false; continue; }
+            // A1, A2 = IFFT(alpha f_hat / G), IFFT(conj(alpha) f_hat / G): members 2d, 2d + 1 of `a` (phase factors on the
+            // load side, straight from f_hat); P_hat = FFT(A1 * A2) over A1 (members 2d, stride 2G)
+            // accounting: the SURVEY 8(d) model attributes 2 array passes per direction to the inverse transforms, 3 to the
+            // product + forward transform and 1 to the accumulate; the path moves more
+            be->mark(BFSM_K_GAIN_INV, 2.0 * c.n * Gc);
+            if (route.seq == GenSeq::Line3) {
+                // the (y,z) passes of the inverse transforms first, then the x-line kernel, then the (y,z) passes of the forward
+                // transform: 14 array moves (8 with the plane kernel).  Its axis passes run z before y backward, y before z forward
+                fft(step(fhat, a, 2 * c.n, +1).load(GEN_PHASE, fb).strides(0, G).from(c.dir0).marks(BFSM_K_GAIN_INV).swapped());
                 line3(c);
                 be->mark(BFSM_K_GAIN_LINE, 0);
-                if (pl) plane(a, nullptr, a, c.n, -1, GEN_PLAIN, 2 * G, 2 * G);
-                else {
-                    pass(a, nullptr, a, c.n, 1, -1, GEN_PLAIN, 2 * G, 2 * G);
-                    be->mark(BFSM_K_GAIN_LINE, 0); pass(a, nullptr, a, c.n, 2, -1, GEN_PLAIN, 2 * G, 2 * G);
-                }
-                GenAccParams<T> ka{a, 2 * G, qhat, dirw, rdir, beta1, c.dir0, c.n, n2stride, first ? 1 : 0, nx, ny, nz};
-                be->mark(BFSM_K_GAIN_FWD, 1.0 * c.n * Gc);
-                be->template launch_gen<GK::Acc, T>((int)((G + GEN_THREADS - 1) / GEN_THREADS), 1, GEN_THREADS, 0, ka);
-                first = false;
-                continue;
+                fft(step(a, a, c.n, -1).strides(2 * G, 2 * G).marks(BFSM_K_GAIN_LINE).swapped());
+            } else {
+                fft(step(fhat, a, 2 * c.n, +1).along(0).load(GEN_PHASE, fb).strides(0, G).from(c.dir0));
+                be->mark(BFSM_K_GAIN_INV, 0);
+                fft(step(a, a, 2 * c.n, +1).marks(BFSM_K_GAIN_INV));
+                // the product is formed on the load side of the first forward pass, then transformed in place
+                be->mark(BFSM_K_GAIN_LINE, 3.0 * c.n * Gc);
+                fft(step(a, a, c.n, -1).load(GEN_PRODUCT, a + G).strides(2 * G, 2 * G).marks(BFSM_K_GAIN_LINE));
+                be->mark(BFSM_K_GAIN_LINE, 0);
+                fft(step(a, a, c.n, -1).along(0).strides(2 * G, 2 * G));
             }
-            // A1, A2 = IFFT(alpha f_hat / G), IFFT(conj(alpha) f_hat / G): members 2d, 2d + 1 of `a`
-            // accounting: the SURVEY 8(d) model attributes 2 array passes per direction to this group (the inverse
-            // transforms), 3 to the next (product + forward transform) and 1 to the accumulate; the path moves more
-            be->mark(BFSM_K_GAIN_INV, 2.0 * c.n * Gc);
-            pass(fhat, fb, a, nb2, 0, +1, GEN_PHASE, 0, G, c.dir0);
-            if (pl) { be->mark(BFSM_K_GAIN_INV, 0); plane(a, nullptr, a, nb2, +1, GEN_PLAIN, G, G); }
-            else {
-                be->mark(BFSM_K_GAIN_INV, 0); pass(a, nullptr, a, nb2, 1, +1, GEN_PLAIN, G, G);
-                be->mark(BFSM_K_GAIN_INV, 0); pass(a, nullptr, a, nb2, 2, +1, GEN_PLAIN, G, G);
-            }
-            // P_hat = FFT(A1 * A2): the product is formed on the load side of the first forward pass and written over
-            // A1 (members 2d, stride 2G), then transformed in place
-            be->mark(BFSM_K_GAIN_LINE, 3.0 * c.n * Gc);
-            if (pl) plane(a, a + G, a, c.n, -1, GEN_PRODUCT, 2 * G, 2 * G);
-            else {
-                pass(a, a + G, a, c.n, 2, -1, GEN_PRODUCT, 2 * G, 2 * G);
-                be->mark(BFSM_K_GAIN_LINE, 0); pass(a, nullptr, a, c.n, 1, -1, GEN_PLAIN, 2 * G, 2 * G);
-            }
-            be->mark(BFSM_K_GAIN_LINE, 0); pass(a, nullptr, a, c.n, 0, -1, GEN_PLAIN, 2 * G, 2 * G);
-            GenAccParams<T> ka{a, 2 * G, qhat, dirw, rdir, beta1, c.dir0, c.n, n2stride, first ? 1 : 0, nx, ny, nz};
             be->mark(BFSM_K_GAIN_FWD, 1.0 * c.n * Gc);
-            be->template launch_gen<GK::Acc, T>((int)((G + GEN_THREADS - 1) / GEN_THREADS), 1, GEN_THREADS, 0, ka);
+            accumulate(a, 2 * G, c.n, c.dir0, first, true);
             first = false;
         }
         if (first) {   // empty shard: qhat = 0
-            GenAccParams<T> ka{a, 2 * G, qhat, dirw, rdir, beta1, 0, 0, n2stride, 1, nx, ny, nz, 0, G};
             be->mark(-1, 0);
-            be->template launch_gen<GK::Acc, T>((int)((G + GEN_THREADS - 1) / GEN_THREADS), nb, GEN_THREADS, 0, ka);
+            accumulate(a, 2 * G, 0, 0, true, true, nb, 0, G);
         }
     }
 
@@ -1358,26 +1338,16 @@ struct GenericPipeline {
         cx<T>* tg = tail;                                   // [max_batch][G] gain, then [max_batch][G] loss
         cx<T>* tl = tail + (size_t)max_batch * G;
         be->mark(BFSM_K_TAIL, (with_loss ? 7.0 : 3.5) * nb * Gc);
-        const bool pl = plane_ok();
-        auto yz = [&](cx<T>* t) {
-            if (pl) { be->mark(BFSM_K_TAIL, 0); plane(t, nullptr, t, nb, +1, GEN_PLAIN, G, G); }
-            else {
-                be->mark(BFSM_K_TAIL, 0); pass(t, nullptr, t, nb, 1, +1, GEN_PLAIN, G, G);
-                be->mark(BFSM_K_TAIL, 0); pass(t, nullptr, t, nb, 2, +1, GEN_PLAIN, G, G);
-            }
-        };
         if (with_loss) {
             // gain and loss term through the same launches: slot s of member m at tail + (s max_batch + m) G
             const size_t half = (size_t)max_batch * G;
-            pass(qhat, loss_hat ? loss_hat : fhat, tail, 2 * nb, 0, +1, GEN_TAIL2, 0, half, 0, 2, G, G);
-            if (pl) { be->mark(BFSM_K_TAIL, 0); plane(tail, nullptr, tail, 2 * nb, +1, GEN_PLAIN, G, G, 0, nb, half, half); }
-            else {
-                be->mark(BFSM_K_TAIL, 0); pass(tail, nullptr, tail, 2 * nb, 1, +1, GEN_PLAIN, G, G, 0, nb, half, half);
-                be->mark(BFSM_K_TAIL, 0); pass(tail, nullptr, tail, 2 * nb, 2, +1, GEN_PLAIN, G, G, 0, nb, half, half);
-            }
+            fft(step(qhat, tail, 2 * nb, +1).along(0).load(GEN_TAIL2, loss_hat ? loss_hat : fhat).strides(0, half).members(2, G, G));
+            be->mark(BFSM_K_TAIL, 0);
+            fft(step(tail, tail, 2 * nb, +1).members(nb, half, half).marks(BFSM_K_TAIL));
         } else {
-            pass(qhat, nullptr, tg, nb, 0, +1, GEN_PLAIN, G, G);
-            yz(tg);
+            fft(step(qhat, tg, nb, +1).along(0));
+            be->mark(BFSM_K_TAIL, 0);
+            fft(step(tg, tg, nb, +1).marks(BFSM_K_TAIL));
         }
         const size_t tot = (size_t)nb * G;                  // members are contiguous in every array involved
         GenCombineParams<T> kc{tg, tl, f_dev, Q_dev, tot, with_loss ? 1 : 0};
@@ -1398,12 +1368,9 @@ struct GenericPipeline {
         spectrum(f_dev, fhat, nb);
         cx<T>* tl = tail + (size_t)max_batch * G;
         be->mark(BFSM_K_TAIL, 3.5 * nb * Gc);
-        pass(fhat, nullptr, tl, nb, 0, +1, GEN_BETA2, G, G);
-        if (plane_ok()) { be->mark(BFSM_K_TAIL, 0); plane(tl, nullptr, tl, nb, +1, GEN_PLAIN, G, G); }
-        else {
-            be->mark(BFSM_K_TAIL, 0); pass(tl, nullptr, tl, nb, 1, +1, GEN_PLAIN, G, G);
-            be->mark(BFSM_K_TAIL, 0); pass(tl, nullptr, tl, nb, 2, +1, GEN_PLAIN, G, G);
-        }
+        fft(step(fhat, tl, nb, +1).along(0).load(GEN_BETA2));
+        be->mark(BFSM_K_TAIL, 0);
+        fft(step(tl, tl, nb, +1).marks(BFSM_K_TAIL));
         const size_t tot = (size_t)nb * G;
         GenCombineParams<T> kc{tl, tl, nullptr, nu_dev, tot, 0};
         be->mark(BFSM_K_TAIL, 0);
@@ -1412,18 +1379,11 @@ struct GenericPipeline {
 
     // In-place batched 3-D transform on user data (bfsm_fft3d); natural layouts on both sides
     int fft3d(cx<T>* data, int batch, int sign) {
-        if (plane_ok()) {
-            if (sign < 0) { be->mark(-1, 0); plane(data, nullptr, data, batch, -1, GEN_PLAIN, G, G); }
-            be->mark(-1, 0);
-            pass(data, nullptr, data, batch, 0, sign, GEN_PLAIN, G, G);
-            if (sign > 0) { be->mark(-1, 0); plane(data, nullptr, data, batch, +1, GEN_PLAIN, G, G); }
-            return BFSM_OK;
-        }
-        const int order[3] = {2, 1, 0};
-        for (int i = 0; i < 3; ++i) {
-            be->mark(-1, 0);
-            pass(data, nullptr, data, batch, sign < 0 ? order[i] : order[2 - i], sign, GEN_PLAIN, G, G);
-        }
+        const Step s = step(data, data, batch, sign);
+        if (sign < 0) { be->mark(-1, 0); fft(s); }
+        be->mark(-1, 0);
+        fft(Step(s).along(0));
+        if (sign > 0) { be->mark(-1, 0); fft(s); }
         return BFSM_OK;
     }
 };

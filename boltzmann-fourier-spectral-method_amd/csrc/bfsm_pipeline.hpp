@@ -115,15 +115,20 @@ inline int target_workgroups(int N, int max_batch = 1) {
     return single / nb > 512 ? single / nb : 512;
 }
 
+// The shard of a handle in full quadrature directions b = r * n_sph + s: [dir_begin, dir_end), or all of them (0, 0)
+inline void shard_range(const bfsm_desc& d, long long& begin, long long& end) {
+    const long long B = (long long)d.n_gl * d.n_sph;
+    if (d.dir_begin == 0 && d.dir_end == 0) { begin = 0; end = B; }
+    else { begin = d.dir_begin; end = d.dir_end; }
+}
+
 inline PlanInfo make_plan(const bfsm_desc& d) {
     PlanInfo p;
     p.N = d.nvx;
     p.precision = d.precision;
     p.n_gl = d.n_gl;
     p.n_sph = d.n_sph;
-    const long long B = (long long)d.n_gl * d.n_sph;
-    if (d.dir_begin == 0 && d.dir_end == 0) { p.full_begin = 0; p.full_end = B; }
-    else { p.full_begin = d.dir_begin; p.full_end = d.dir_end; }
+    shard_range(d, p.full_begin, p.full_end);
     p.exact_reductions = (d.flags & BFSM_FLAG_EXACT_REDUCTIONS) != 0;
     p.hermitian = p.exact_reductions && (d.flags & BFSM_FLAG_HERMITIAN) != 0;
     p.sph_eff = d.n_sph;
@@ -220,55 +225,77 @@ struct HostTables {
     std::vector<T> beta2;                  // [n2stride]
 };
 
+// The pieces of the host tables, shared by build_tables() and GenericPipeline::init: one copy of the reference's formulas
+constexpr double TABLE_PI = 3.14159265358979323846;  // Utilities/constants.hpp:7
+constexpr long double TABLE_PI_L = 3.141592653589793238462643383279502884L;
+// exp(-2 pi i k / n), k < n
+template <typename T>
+std::vector<cx<T>> twiddle_table(int n) {
+    std::vector<cx<T>> tw(n);
+    for (int k = 0; k < n; ++k) {
+        const long double a = -2.0L * TABLE_PI_L * (long double)k / (long double)n;
+        tw[k] = {(T)cosl(a), (T)sinl(a)};
+    }
+    return tw;
+}
+// theta(l) = -(pi/(2L)) rho_r (l . sigma_s)   (FFTWBoltzmannOperator.cpp:205-209) is separable in lx, ly, lz: the factor k of
+// radial node r, and one direction's row exp(i k l sigma) along an axis of n points, l the FFT-order mode (cpp:50-57).
+// scale: a factor applied in double; null: the value narrows straight to T.
+inline long double phase_k(const bfsm_desc& d, int r) {
+    return -((long double)TABLE_PI / (2.0L * (long double)d.L)) * (long double)d.gl_nodes[r];
+}
+template <typename T>
+void phase_row(cx<T>* dst, int n, long double k, double sigma, const double* scale) {
+    for (int j = 0; j < n; ++j) {
+        const int l = j < n / 2 ? j : j - n;
+        const long double a = k * (long double)l * (long double)sigma;
+        if (scale) dst[j] = {(T)(*scale * (double)cosl(a)), (T)(*scale * (double)sinl(a))};
+        else dst[j] = {(T)cosl(a), (T)sinl(a)};
+    }
+}
+// weight = fft_scale * gl_wts[r] * spherical_wts[s] * pow(gl_nodes[r], gamma + 2)   (cpp:252)
+inline double direction_weight(const bfsm_desc& d, int r, int s, double fft_scale) {
+    return fft_scale * d.gl_wts[r] * d.sph_wts[s] * std::pow(d.gl_nodes[r], d.gamma + 2);
+}
+// beta1 [n_gl][n2stride] and beta2 [n2stride] over |l|^2 = n2
+template <typename T>
+void beta_tables(const bfsm_desc& d, int n2stride, double fft_scale, std::vector<T>& beta1, std::vector<T>& beta2) {
+    const double pi = TABLE_PI;
+    beta1.resize((size_t)d.n_gl * n2stride);
+    beta2.resize((size_t)n2stride);
+    for (int n2 = 0; n2 < n2stride; ++n2) {
+        const double norm_l = std::sqrt((double)n2);
+        double b2 = 0;
+        for (int r = 0; r < d.n_gl; ++r) {
+            // beta1 = 4 pi b_gamma sincc(pi rho_r |l| / (2L))   (cpp:261-262)
+            beta1[(size_t)r * n2stride + n2] = (T)(4 * pi * d.b_gamma * sincc_ref(pi * d.gl_nodes[r] * norm_l / (2 * d.L)));
+            // beta2 += 16 pi^2 b_gamma w_r rho_r^(gamma+2) sincc(pi rho_r |l| / L)   (cpp:290-293)
+            b2 += 16 * pi * pi * d.b_gamma * d.gl_wts[r] * std::pow(d.gl_nodes[r], d.gamma + 2) *
+                  sincc_ref(pi * d.gl_nodes[r] * norm_l / d.L);
+        }
+        beta2[n2] = (T)(fft_scale * b2);   // cpp:295-296 folds fft_scale
+    }
+}
+
 template <typename T>
 HostTables<T> build_tables(const bfsm_desc& d, const PlanInfo& p) {
     HostTables<T> t;
     const int N = p.N;
-    const double pi = 3.14159265358979323846;  // Utilities/constants.hpp:7
-    const long double PI_L = 3.141592653589793238462643383279502884L;
-    const double G = (double)p.G();
-    const double fft_scale = 1.0 / G;          // FFTWBoltzmannOperator.cpp:162
-    t.tw.resize(N);
-    for (int n = 0; n < N; ++n) {
-        const long double a = -2.0L * PI_L * (long double)n / (long double)N;
-        t.tw[n] = {(T)cosl(a), (T)sinl(a)};
-    }
+    const double fft_scale = 1.0 / (double)p.G();   // FFTWBoltzmannOperator.cpp:162
+    t.tw = twiddle_table<T>(N);
     const long long nd = p.n_dirs();
-    t.phx.resize((size_t)nd * N);
-    t.phy.resize((size_t)nd * N);
-    t.phz.resize((size_t)nd * N);
+    t.phx.resize((size_t)nd * N); t.phy.resize((size_t)nd * N); t.phz.resize((size_t)nd * N);
     t.dirw.resize((size_t)nd);
     for (long long i = 0; i < nd; ++i) {
         const long long b = p.dir_begin + i;
         const int r = (int)(b / p.sph_eff), s = (int)(b % p.sph_eff);   // s < n_sph/2 when antipodal pairs are merged
-        // theta(l) = -(pi/(2L)) rho_r (l . sigma_s)   (FFTWBoltzmannOperator.cpp:205-209), separable in lx, ly, lz
-        const long double k = -((long double)pi / (2.0L * (long double)d.L)) * (long double)d.gl_nodes[r];
-        for (int n = 0; n < N; ++n) {
-            const int l = n < N / 2 ? n : n - N;   // FFT-order mode (FFTWBoltzmannOperator.cpp:50-57)
-            const long double ax = k * (long double)l * (long double)d.sx[s];
-            const long double ay = k * (long double)l * (long double)d.sy[s];
-            const long double az = k * (long double)l * (long double)d.sz[s];
-            t.phx[(size_t)i * N + n] = {(T)(fft_scale * (double)cosl(ax)), (T)(fft_scale * (double)sinl(ax))};
-            t.phy[(size_t)i * N + n] = {(T)cosl(ay), (T)sinl(ay)};
-            t.phz[(size_t)i * N + n] = {(T)cosl(az), (T)sinl(az)};
-        }
-        // weight = fft_scale * gl_wts[r] * spherical_wts[s] * pow(gl_nodes[r], gamma + 2)   (cpp:252)
-        t.dirw[(size_t)i] = (T)(p.weight_mult * (fft_scale * d.gl_wts[r] * d.sph_wts[s] * std::pow(d.gl_nodes[r], d.gamma + 2)));
+        const long double k = phase_k(d, r);
+        phase_row(&t.phx[(size_t)i * N], N, k, d.sx[s], &fft_scale);
+        phase_row(&t.phy[(size_t)i * N], N, k, d.sy[s], nullptr);
+        phase_row(&t.phz[(size_t)i * N], N, k, d.sz[s], nullptr);
+        t.dirw[(size_t)i] = (T)(p.weight_mult * (direction_weight(d, r, s, fft_scale)));
     }
-    t.beta1.resize((size_t)d.n_gl * p.n2stride);
-    t.beta2.assign((size_t)p.n2stride, (T)0);
-    std::vector<double> b2((size_t)p.n2stride, 0.0);
-    for (int n2 = 0; n2 < p.n2stride; ++n2) {
-        const double norm_l = std::sqrt((double)n2);
-        for (int r = 0; r < d.n_gl; ++r) {
-            // beta1 = 4 pi b_gamma sincc(pi rho_r |l| / (2L))   (cpp:261-262)
-            t.beta1[(size_t)r * p.n2stride + n2] = (T)(4 * pi * d.b_gamma * sincc_ref(pi * d.gl_nodes[r] * norm_l / (2 * d.L)));
-            // beta2 += 16 pi^2 b_gamma w_r rho_r^(gamma+2) sincc(pi rho_r |l| / L)   (cpp:290-293)
-            b2[n2] += 16 * pi * pi * d.b_gamma * d.gl_wts[r] * std::pow(d.gl_nodes[r], d.gamma + 2) *
-                      sincc_ref(pi * d.gl_nodes[r] * norm_l / d.L);
-        }
-        t.beta2[n2] = (T)(fft_scale * b2[n2]);   // cpp:295-296 folds fft_scale
-    }
+    beta_tables(d, p.n2stride, fft_scale, t.beta1, t.beta2);
     return t;
 }
 
@@ -350,14 +377,35 @@ bool for_fused_n(int N, F&& fn) {
     }
 }
 
+// The device allocations of one handle (Pipeline, GenericPipeline): every buffer is made here, so release_owned() frees
+// exactly what init made.
+template <class Backend>
+struct DeviceBuffers {
+    Backend* be = nullptr;
+    std::vector<void*> owned;     // every device allocation of this handle
+    template <typename U>
+    bool dev_alloc(U*& dst, size_t n) {
+        dst = (U*)be->alloc(n * sizeof(U));
+        if (dst) owned.push_back(dst);
+        return dst != nullptr;
+    }
+    template <typename U>
+    bool dev_copy(U*& dst, const std::vector<U>& src) {
+        if (!dev_alloc(dst, src.empty() ? 1 : src.size())) return false;
+        if (!src.empty()) be->upload(dst, src.data(), src.size() * sizeof(U));
+        return true;
+    }
+    void release_owned() { for (void* p : owned) be->release(p); owned.clear(); }
+};
+
 // Device-resident state of one handle.  `Backend` supplies:
 //   void* alloc(size_t), void release(void*), void upload(void* dst, const void* src, size_t), void zero(void*, size_t)
 //   template <K kind, typename T, class P> void launch(int grid_x, int grid_y, int grid_z, const P& params, int N)
 //   void mark(int kind, double alg_bytes)              -- accounting tag of the next launch (kind < 0: untracked)
 template <typename T, class Backend>
-struct Pipeline {
+struct Pipeline : DeviceBuffers<Backend> {
+    using DeviceBuffers<Backend>::be; using DeviceBuffers<Backend>::dev_alloc; using DeviceBuffers<Backend>::dev_copy;
     PlanInfo plan;
-    Backend* be = nullptr;
     // device buffers
     cx<T>* fhat = nullptr;
     cx<T>* tg = nullptr;          // the tail's gain and loss arrays: one block [2][max_batch G], tl = tg + max_batch G
@@ -385,21 +433,6 @@ struct Pipeline {
     // N = 16 whole-direction path: one partial Q_hat per workgroup
     T* small_part = nullptr;      // [small_wgs + 1][G] real partial results
     int small_wgs = 0, small_per = 0;
-
-    std::vector<void*> owned;     // every device allocation of this pipeline: what destroy() releases
-
-    template <typename U>
-    bool dev_alloc(U*& dst, size_t n) {
-        dst = (U*)be->alloc(n * sizeof(U));
-        if (dst) owned.push_back(dst);
-        return dst != nullptr;
-    }
-    template <typename U>
-    bool dev_copy(U*& dst, const std::vector<U>& src) {
-        if (!dev_alloc(dst, src.empty() ? 1 : src.size())) return false;
-        if (!src.empty()) be->upload(dst, src.data(), src.size() * sizeof(U));
-        return true;
-    }
 
     // A1' / A2' interleaved per element in one array (bfsm_core.hpp, ab_interleaved)
     bool pair_geometry() const { return plan.N == 128 && ab_interleaved<128, T>(); }
@@ -483,7 +516,7 @@ struct Pipeline {
 
     void destroy() {
         if (!be) return;
-        for (void* p : owned) be->release(p);
+        this->release_owned();
         *this = Pipeline();       // no pointer to released memory survives
     }
 
