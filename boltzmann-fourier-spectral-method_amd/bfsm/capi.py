@@ -12,6 +12,9 @@ BFSM_FLAG_NO_SMALL_PATH = 8
 BFSM_FLAG_CONSERVE = 16
 KERNEL_NAMES = ("fft_f", "gain_inv", "gain_line", "gain_fwd", "reduce", "tail")
 K_COUNT = len(KERNEL_NAMES)
+# columns of a bfsm_moments_async row (include/bfsm.h: BFSM_MOM_*)
+MOM_RHO, MOM_MX, MOM_MY, MOM_MZ, MOM_E, MOM_UX, MOM_UY, MOM_UZ, MOM_T, MOM_H = range(10)
+MOM_COUNT = 10
 
 # every symbol include/bfsm.h declares (checked by tests/test_capi_symbols.py)
 EXPORTED_SYMBOLS = (
@@ -22,6 +25,7 @@ EXPORTED_SYMBOLS = (
     "bfsm_conserve_async",
     "bfsm_collide_split", "bfsm_collide_split_async", "bfsm_collide_split_batch_partial_async",
     "bfsm_collide_bilinear_split_partial_async", "bfsm_loss_rate_async",
+    "bfsm_moments_async", "bfsm_maxwellian_async",
 )
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -107,12 +111,14 @@ def load_library(path=None):
     L.bfsm_collide_bilinear_partial_async.restype = ctypes.c_int
     L.bfsm_conserve_async.argtypes = [vp, vp, ctypes.c_int, vp]
     L.bfsm_conserve_async.restype = ctypes.c_int
-    # the gain / loss split: typed where the library has it (the presence of the symbols is the capability check, so that an
+    # the gain / loss split, the moments and the Maxwellian: typed where the library has them (the presence of the symbols is the capability check, so that an
     # older build named by BFSM_LIB still loads)
     for name, args in (("bfsm_collide_split", [vp, vp, vp, vp]), ("bfsm_collide_split_async", [vp, vp, vp, vp, vp]),
                        ("bfsm_collide_split_batch_partial_async", [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp]),
                        ("bfsm_collide_bilinear_split_partial_async", [vp, vp, vp, vp, vp, ctypes.c_int, vp]),
-                       ("bfsm_loss_rate_async", [vp, vp, vp, ctypes.c_int, vp])):
+                       ("bfsm_loss_rate_async", [vp, vp, vp, ctypes.c_int, vp]),
+                       ("bfsm_moments_async", [vp, vp, vp, ctypes.c_int, vp]),
+                       ("bfsm_maxwellian_async", [vp, vp, vp, ctypes.c_int, vp])):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes = args

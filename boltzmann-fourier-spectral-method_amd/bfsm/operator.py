@@ -260,6 +260,26 @@ class HIPBoltzmannOperator:
             raise ValueError("Q must be a contiguous float64 CUDA tensor with n_batch*Nvx*Nvy*Nvz elements")
         self._check(self._lib.bfsm_conserve_async(self._h, _ptr(Q), int(n_batch), ctypes.c_void_p(stream)))
 
+    # Macroscopic state of f and its Maxwellian (include/bfsm.h, bfsm_moments_async / bfsm_maxwellian_async): rows of
+    # capi.MOM_COUNT doubles (capi.MOM_RHO ... capi.MOM_H) in device memory, so moments -> maxwellian needs no host round trip.
+    def _require_rows(self, mom, n_batch):
+        if not (mom.is_cuda and mom.dtype.is_floating_point and mom.element_size() == 8 and mom.is_contiguous()
+                and mom.numel() == int(n_batch) * capi.MOM_COUNT):
+            raise ValueError("mom must be a contiguous float64 CUDA tensor with n_batch*MOM_COUNT elements")
+
+    def moments(self, mom, f, n_batch=1, stream=0):
+        """mom[i] = (rho, m, E, u, T, H) of f[i] for n_batch distributions; any handle; enqueued on `stream`."""
+        self._require_batch(n_batch, f)
+        self._require_rows(mom, n_batch)
+        self._check(self._lib.bfsm_moments_async(self._h, _ptr(mom), _ptr(f), int(n_batch), ctypes.c_void_p(stream)))
+
+    def maxwellian(self, M, mom, n_batch=1, stream=0):
+        """M[i] = the Maxwellian of rho, u, T of row mom[i] on the grid (0 where rho or T is not finite and positive); any
+        handle; enqueued on `stream`."""
+        self._require_batch(n_batch, M)
+        self._require_rows(mom, n_batch)
+        self._check(self._lib.bfsm_maxwellian_async(self._h, _ptr(M), _ptr(mom), int(n_batch), ctypes.c_void_p(stream)))
+
     def qhatBuffer(self):
         """(device pointer, n_elems, precision) of the partial Q_gain_hat owned by the handle."""
         n = ctypes.c_size_t()

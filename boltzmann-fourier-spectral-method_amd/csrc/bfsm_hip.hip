@@ -12,6 +12,7 @@
 #include "bfsm_pipeline.hpp"
 #include "bfsm_generic.hpp"
 #include "bfsm_conserve.hpp"
+#include "bfsm_moments.hpp"
 #include "bfsm_calls.hpp"
 
 #ifndef BFSM_F32_N64_WAVES
@@ -372,6 +373,14 @@ __global__ void __launch_bounds__(CONS_THREADS) bfsm_cons_kernel(const ConsParam
     BFSM_RUN_CONS_BODY(kind, prm, ctx)
 }
 
+// macroscopic state of f (bfsm_moments.hpp): 256 threads, 12 KiB of LDS
+template <MK kind>
+__global__ void __launch_bounds__(MOM_THREADS) bfsm_mom_kernel(const MomParams prm) {
+    extern __shared__ __align__(16) unsigned char bfsm_smem[];
+    DevCtx ctx{bfsm_smem};
+    BFSM_RUN_MOM_BODY(kind, prm, ctx)
+}
+
 // ---- HIP backend -----------------------------------------------------------------------------------------------
 struct HipBackend {
     hipStream_t stream = nullptr;
@@ -466,6 +475,12 @@ struct HipBackend {
         launch_any(reinterpret_cast<const void*>(bfsm_cons_kernel<kind>), gx, gy, 1, CONS_THREADS, CONS_LDS_BYTES, &prm, opted);
     }
 
+    template <MK kind>
+    void launch_mom(int gx, int gy, const MomParams& prm) {
+        static std::atomic<unsigned long long> opted{0};
+        launch_any(reinterpret_cast<const void*>(bfsm_mom_kernel<kind>), gx, gy, 1, MOM_THREADS, MOM_LDS_BYTES, &prm, opted);
+    }
+
     template <K kind, typename T, class P>
     void launch(int gx, int gy, int gz, const P& prm, int N) {
         if (gx <= 0 || gy <= 0 || gz <= 0) return;
@@ -489,6 +504,7 @@ struct bfsm_plan {
     bfsm::GenericPipeline<double, bfsm::HipBackend>* g64 = nullptr;   // grids outside the fused pipeline's sizes
     bfsm::GenericPipeline<float, bfsm::HipBackend>* g32 = nullptr;
     bfsm::Conserver<bfsm::HipBackend>* cons = nullptr;   // conservative projection (every handle; BFSM_FLAG_CONSERVE)
+    bfsm::Macroscopic<bfsm::HipBackend>* macro = nullptr;   // moments and Maxwellian of f (every handle)
     bfsm::PlanInfo info;
     size_t G = 0;
     // calls fn(pipeline) on whichever of the four pipelines this handle owns
@@ -593,6 +609,10 @@ static int create_impl(const bfsm_desc* desc, bfsm_handle* out, bfsm_plan*& h) {
     if (rc == BFSM_OK) {
         h->cons = new bfsm::Conserver<bfsm::HipBackend>();
         rc = h->cons->init(*desc, &h->be, err);
+    }
+    if (rc == BFSM_OK) {
+        h->macro = new bfsm::Macroscopic<bfsm::HipBackend>();
+        rc = h->macro->init(*desc, &h->be, err);
     }
     // the descriptor's host arrays are not referenced after create
     h->desc.gl_nodes = h->desc.gl_wts = h->desc.sph_wts = h->desc.sx = h->desc.sy = h->desc.sz = nullptr;
@@ -905,6 +925,50 @@ int bfsm_conserve_async(bfsm_handle h, double* Q_dev, int n_batch, void* stream)
     )
 }
 
+// Moments / entropy rows of n_batch distributions and the Maxwellians of n_batch rows (bfsm_moments.hpp), any handle
+static bool bytes_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+int bfsm_moments_async(bfsm_handle h, double* mom_dev, const double* f_dev, int n_batch, void* stream) {
+    if (!h) return BFSM_ERR_INVALID;
+    BFSM_GUARDED(h,
+        DeviceGuard g(h->desc.device);
+        int rc = enter(h, g, stream);
+        if (rc) return rc;
+        if (!mom_dev || !f_dev) return fail(h, BFSM_ERR_INVALID, "null mom or f");
+        if (((uintptr_t)f_dev & 15) != 0 || ((uintptr_t)mom_dev & 7) != 0)
+            return fail(h, BFSM_ERR_INVALID, "bfsm_moments needs a 16-byte aligned f (and an 8-byte aligned mom)");
+        if (n_batch < 1 || n_batch > h->macro->max_batch)
+            return fail(h, BFSM_ERR_INVALID, "n_batch must be in [1, max_batch of the descriptor]");
+        if (bytes_overlap(mom_dev, (size_t)n_batch * BFSM_MOM_COUNT * sizeof(double), f_dev, (size_t)n_batch * h->G * sizeof(double)))
+            return fail(h, BFSM_ERR_INVALID, "mom must not overlap f");
+        h->be.begin_eval();
+        h->macro->moments(mom_dev, f_dev, n_batch);
+        return leave(h, "bfsm_moments");
+    )
+}
+
+int bfsm_maxwellian_async(bfsm_handle h, double* M_dev, const double* mom_dev, int n_batch, void* stream) {
+    if (!h) return BFSM_ERR_INVALID;
+    BFSM_GUARDED(h,
+        DeviceGuard g(h->desc.device);
+        int rc = enter(h, g, stream);
+        if (rc) return rc;
+        if (!M_dev || !mom_dev) return fail(h, BFSM_ERR_INVALID, "null M or mom");
+        if (((uintptr_t)M_dev & 15) != 0 || ((uintptr_t)mom_dev & 7) != 0)
+            return fail(h, BFSM_ERR_INVALID, "bfsm_maxwellian needs a 16-byte aligned M (and an 8-byte aligned mom)");
+        if (n_batch < 1 || n_batch > h->macro->max_batch)
+            return fail(h, BFSM_ERR_INVALID, "n_batch must be in [1, max_batch of the descriptor]");
+        if (bytes_overlap(M_dev, (size_t)n_batch * h->G * sizeof(double), mom_dev, (size_t)n_batch * BFSM_MOM_COUNT * sizeof(double)))
+            return fail(h, BFSM_ERR_INVALID, "M must not overlap mom");
+        h->be.begin_eval();
+        h->macro->maxwellian(M_dev, mom_dev, n_batch);
+        return leave(h, "bfsm_maxwellian");
+    )
+}
+
 int bfsm_synchronize(bfsm_handle h) {
     if (!h) return BFSM_ERR_INVALID;
     BFSM_GUARDED(h,
@@ -989,6 +1053,7 @@ int bfsm_destroy(bfsm_handle h) {
     if (h->g64) { h->g64->destroy(); delete h->g64; }
     if (h->g32) { h->g32->destroy(); delete h->g32; }
     if (h->cons) { h->cons->destroy(); delete h->cons; }
+    if (h->macro) { h->macro->destroy(); delete h->macro; }
     h->be.destroy_events();
     for (auto& pe : h->pending) (void)hipEventDestroy(pe.ev);
     for (hipEvent_t ev : h->spare_events) (void)hipEventDestroy(ev);

@@ -75,6 +75,10 @@ public:
     const char* lastError() const noexcept;
     // Q := PQ in place for n_batch consecutive device arrays (bfsm_conserve_async), enqueued on `stream`; any handle.
     void conserve(double* Q, int n_batch = 1, void* stream = nullptr);
+    // Macroscopic state of f and its Maxwellian (bfsm_moments_async / bfsm_maxwellian_async): mom = n_batch rows of
+    // BFSM_MOM_COUNT doubles, f and M = n_batch arrays, all device pointers; enqueued on `stream`; any handle.
+    void moments(double* mom, const double* f_in, int n_batch = 1, void* stream = nullptr);
+    void maxwellian(double* M, const double* mom, int n_batch = 1, void* stream = nullptr);
     void* qhatBuffer(size_t* n_elems, int* precision) const;
     void synchronize();
     bfsm_counters counters() const;

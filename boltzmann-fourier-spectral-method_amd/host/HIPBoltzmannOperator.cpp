@@ -94,6 +94,14 @@ void BoltzmannOperator<HIP_Backend>::conserve(double* Q, int n_batch, void* stre
     check(bfsm_conserve_async(handle_, Q, n_batch, stream), "conserve");
 }
 
+void BoltzmannOperator<HIP_Backend>::moments(double* mom, const double* f_in, int n_batch, void* stream) {
+    check(bfsm_moments_async(handle_, mom, f_in, n_batch, stream), "moments");
+}
+
+void BoltzmannOperator<HIP_Backend>::maxwellian(double* M, const double* mom, int n_batch, void* stream) {
+    check(bfsm_maxwellian_async(handle_, M, mom, n_batch, stream), "maxwellian");
+}
+
 void* BoltzmannOperator<HIP_Backend>::qhatBuffer(size_t* n_elems, int* precision) const {
     return bfsm_qhat_buffer(handle_, n_elems, precision);
 }

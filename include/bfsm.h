@@ -267,6 +267,31 @@ int bfsm_loss_rate_async(bfsm_handle h, double* nu_dev, const double* f_dev, int
  * BFSM_ERR_INVALID. */
 int bfsm_conserve_async(bfsm_handle h, double* Q_dev, int n_batch, void* stream);
 
+/*
+ * Macroscopic state of f and its Maxwellian on the device (new functionality; the presence of these symbols is the capability
+ * check, BFSM_VERSION stays 2).  With dV = dx dy dz, d_a = 2L / n_a, and the grid v_a(i) = -L + (i + 1/2) d_a, a row of
+ * BFSM_MOM_COUNT doubles per distribution:
+ *     rho = dV sum f,   m = dV sum v f,   E = dV sum |v|^2 f  (= rho (|u|^2 + 3T)),   u = m / rho,   T = (E / rho - |u|^2) / 3,
+ *     H = dV sum_{f > 0} f log f    (points with f <= 0 contribute 0);        rho == 0 gives u = T = 0.
+ * bfsm_moments_async writes mom_dev[n_batch][BFSM_MOM_COUNT] from f_dev[n_batch][G]; f is not written.
+ * bfsm_maxwellian_async writes M_dev[n_batch][G], M = rho (2 pi T)^(-3/2) exp(-|v - u|^2 / 2T), from rows in DEVICE memory, so
+ * moments -> maxwellian needs no host round trip (what a BGK / ES-BGK closure or a penalized step reads, INTEGRATION.md
+ * section 8).  A caller may fill the rows itself: only BFSM_MOM_RHO, BFSM_MOM_UX..UZ and BFSM_MOM_T are read.  A member whose
+ * rho or T is not finite and positive (an empty or sign-indefinite f) gets M = 0 everywhere: the device cannot report an
+ * error, and the other members of the batch are unaffected.
+ *   - any handle: fused cube, size-generic box, N = 16, BFSM_F32 (the sums are fp64 whatever the transform precision), a
+ *     direction shard, any flags; the results do not depend on any of these.
+ *   - 1 <= n_batch <= max_batch; member i is bitwise the single call on member i on the same handle; repeated calls are
+ *     bitwise identical (fixed-order sums, no atomics; the workgroup count depends on G only).
+ *   - f_dev and M_dev must be 16-byte aligned.  BFSM_ERR_INVALID, with a message and nothing written: a null or misaligned
+ *     pointer, a bad n_batch, mom overlapping f, M overlapping mom.
+ *   - allocation-free after bfsm_create, graph-capturable and tracked by bfsm_synchronize like the other _async entry points.
+ */
+enum { BFSM_MOM_RHO = 0, BFSM_MOM_MX = 1, BFSM_MOM_MY = 2, BFSM_MOM_MZ = 3, BFSM_MOM_E = 4, BFSM_MOM_UX = 5, BFSM_MOM_UY = 6,
+       BFSM_MOM_UZ = 7, BFSM_MOM_T = 8, BFSM_MOM_H = 9, BFSM_MOM_COUNT = 10 };
+int bfsm_moments_async(bfsm_handle h, double* mom_dev, const double* f_dev, int n_batch, void* stream);
+int bfsm_maxwellian_async(bfsm_handle h, double* M_dev, const double* mom_dev, int n_batch, void* stream);
+
 /* Blocks until everything enqueued by this handle has completed: the work of every stream that was passed to one of
  * its entry points since the previous bfsm_synchronize is waited for (through events the handle recorded itself), not
  * only the most recent one; every distinct stream is tracked, however many.  The list is cleared whether or not the
