@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = (
     "bfsm_collide_split", "bfsm_collide_split_async", "bfsm_collide_split_batch_partial_async",
     "bfsm_collide_bilinear_split_partial_async", "bfsm_loss_rate_async",
     "bfsm_moments_async", "bfsm_maxwellian_async",
+    "bfsm_collide_symmetric", "bfsm_collide_symmetric_async", "bfsm_collide_symmetric_partial_async",
 )
 
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -118,7 +119,9 @@ def load_library(path=None):
                        ("bfsm_collide_bilinear_split_partial_async", [vp, vp, vp, vp, vp, ctypes.c_int, vp]),
                        ("bfsm_loss_rate_async", [vp, vp, vp, ctypes.c_int, vp]),
                        ("bfsm_moments_async", [vp, vp, vp, ctypes.c_int, vp]),
-                       ("bfsm_maxwellian_async", [vp, vp, vp, ctypes.c_int, vp])):
+                       ("bfsm_maxwellian_async", [vp, vp, vp, ctypes.c_int, vp]),
+                       ("bfsm_collide_symmetric", [vp, vp, vp, vp]), ("bfsm_collide_symmetric_async", [vp, vp, vp, vp, vp]),
+                       ("bfsm_collide_symmetric_partial_async", [vp, vp, vp, vp, ctypes.c_int, vp])):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes = args

@@ -176,6 +176,26 @@ class HIPBoltzmannOperator:
         self.computeBilinearCollision(tmp, h, f)
         Q.add_(tmp.view(Q.shape))
 
+    # Symmetric form Qs(g, f) = Q(g, f) + Q(f, g) (include/bfsm.h, bfsm_collide_symmetric*): one call on ANY handle, the exact and
+    # Hermitian modes included; L_f[h] = Qs(f, h), Qs(f, f) = 2 Q(f, f).
+    def computeSymmetricCollision(self, Q, g, f):
+        """Blocking Q = Q(g, f) + Q(f, g), device tensors; needs a handle that owns all directions."""
+        self._require(g, Q)
+        self._require(f)
+        self._check(self._lib.bfsm_collide_symmetric(self._h, _ptr(Q), _ptr(g), _ptr(f)))
+
+    def computeSymmetricCollisionAsync(self, Q, g, f, stream=0):
+        self._require(g, Q)
+        self._require(f)
+        self._check(self._lib.bfsm_collide_symmetric_async(self._h, _ptr(Q), _ptr(g), _ptr(f), ctypes.c_void_p(stream)))
+
+    def collideSymmetricPartial(self, Q, g, f, with_loss, stream=0):
+        """This shard's part of Q(g, f) + Q(f, g) [- both loss terms if with_loss]; the caller sums Q over the ranks."""
+        self._require(g, Q)
+        self._require(f)
+        self._check(self._lib.bfsm_collide_symmetric_partial_async(self._h, _ptr(Q), _ptr(g), _ptr(f), 1 if with_loss else 0,
+                                                                   ctypes.c_void_p(stream)))
+
     # Gain / loss split (include/bfsm.h, bfsm_collide_split*): Qgain = the gain Q+, nu = the collision frequency nu[f], so that
     # Q = Qgain - f * nu (bilinear form: Qgain - g * nu).  BFSM_FLAG_CONSERVE has no effect on them.
     def _require_batch(self, n_batch, *tensors):

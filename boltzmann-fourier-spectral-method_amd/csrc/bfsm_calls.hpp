@@ -40,6 +40,29 @@ void collide_split(Pipe& p, double* Qgain, double* nu, const double* f, int n_ba
     });
 }
 
+// Qs(g,f) = Q(g,f) + Q(f,g) of the shard [- both loss terms] for one distribution pair (bfsm_collide_symmetric*_async), on every
+// kind of handle.  Fused cubes, every mode (Pipeline::collide_symmetric): two gain passes per chunk with the spectra exchanged
+// into doubled segment sums and slabs, one KC, one reduce, one three-plane tail; N = 16 takes the plane-tile pipeline.
+// Size-generic boxes (GenericPipeline::collide_symmetric): the bilinear gain launches twice, the second pass accumulating onto
+// the first one's Q_hat, one tail with both loss terms.
+template <class Pipe>
+void collide_symmetric(Pipe& p, double* Q, const double* g, const double* f, bool with_loss) {
+    p.collide_symmetric(Q, g, f, with_loss);
+}
+
+// Bytes the symmetric call moves on the fused pipeline (model; the counterpart of moved_bytes_per_eval): per effective direction
+// four stored A' arrays written once and read once (two passes of A1', A2'; h = the stored share of the planes, (N/2 + 1)/N on
+// Hermitian handles), twice the segment sums and slabs, two transforms of an input and a three-plane tail (9 + 6.5 arrays).
+// The per-direction route of the faithful mode moves 12 n + 4 sg.  Two faithful bilinear calls move 2 (4 n_full + 4 sg + 9).
+inline double symmetric_moved_bytes_per_eval(const PlanInfo& p) {
+    const double c = p.precision == BFSM_F64 ? 16.0 : 8.0;
+    const double G = (double)p.G(), n = (double)p.n_dirs(), sg = (double)p.segs.size();
+    if (p.N == 0) return (2.0 * (double)p.gen_moves * n + 4.0 * p.gen_slabs + (p.gen_plane ? 28.0 : 42.0)) * G * c;
+    const double h = p.hermitian ? (double)(p.N / 2 + 1) / p.N : 1.0;
+    const bool sums = p.exact_reductions || (p.precision == BFSM_F64 ? kb_sums_segments_n<double>(p.N) : kb_sums_segments_n<float>(p.N));
+    return ((sums ? 8.0 * n * h + 8.0 * sg : 12.0 * n + 4.0 * sg) + 15.5) * G * c;
+}
+
 // nu alone (bfsm_loss_rate_async)
 template <class Pipe>
 void loss_rate(Pipe& p, double* nu, const double* f, int n_batch) {

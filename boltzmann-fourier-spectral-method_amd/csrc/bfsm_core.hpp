@@ -541,6 +541,17 @@ struct GainInvNyqParams {    // KA + guest KN workgroups
     int ka_groups;           // blockIdx.y below this: KA
 };
 
+// KA + guest KN workgroups of the symmetric form Qs(g,f) on a Hermitian handle (bfsm_collide_symmetric*): both kernels take
+// the alpha operand from ka.fhat and the conj(alpha) operand from ka.fhat2.  A type of its own, like GainInvBiParams.
+template <typename T>
+struct GainInvNyqBiParams {
+    GainInvBiParams<T> ka;
+    cx<T>* r;
+    size_t r_bstride;
+    int kn_blocks;
+    int ka_groups;
+};
+
 template <typename T>
 struct GainLineParams {      // KB
     cx<T>* a1;               // in: A1' (ab_interleaved: the pairs {A1', A2'})
@@ -621,6 +632,14 @@ struct NyqRowsParams {       // KN: R[slot][sign][kind][j][N], j = idx - (N/2 + 
     size_t r_bstride;        // batch stride (elements) of r
 };
 
+// KN of the symmetric form: the rows of sign 0 (alpha) come from fhat, the rows of sign 1 (conj alpha) from fhat2
+template <typename T>
+struct NyqRowsBiParams : NyqRowsParams<T> {
+    const cx<T>* fhat2;      // [lx][lz][ly]
+};
+template <class P> struct kn_bilinear { static constexpr bool value = false; };
+template <typename T> struct kn_bilinear<NyqRowsBiParams<T>> { static constexpr bool value = true; };
+
 template <typename T>
 struct GainLineAccHParams {  // KB' in the Hermitian mode
     const cx<T>* a1;         // [slot][N/2 + 1 planes][y][z]
@@ -680,6 +699,23 @@ struct TailLineSplitParams : TailLineParams<T> {
 };
 template <class P> struct tail_split { static constexpr bool value = false; };
 template <typename T> struct tail_split<TailLineSplitParams<T>> { static constexpr bool value = true; };
+// Symmetric form Qs(g,f) = Q(g,f) + Q(f,g) (include/bfsm.h, bfsm_collide_symmetric*): two loss terms.  Tail step 1 with a third
+// plane (grid.y = 3): y == 1 forms beta2 * fhat as before, y == 2 beta2 * (fhat + fhat2_off) into tg + tl2_off.  Tail step 2
+// reads the three arrays: Q = Re(gain) - Re(loss 1) * f - Re(loss 2) * f2.  Parameter types of their own, as above.
+template <typename T>
+struct TailInvSymParams : TailInvParams<T> {
+    long long fhat2_off;     // the second loss spectrum, as an element offset from fhat
+    long long tl2_off;       // the second loss array, as an element offset from tg
+};
+template <class P> struct tail_inv_sym { static constexpr bool value = false; };
+template <typename T> struct tail_inv_sym<TailInvSymParams<T>> { static constexpr bool value = true; };
+template <typename T>
+struct TailLineSymParams : TailLineParams<T> {
+    const cx<T>* tl2;        // the second loss array
+    const double* f2;        // multiplies it
+};
+template <class P> struct tail_line_sym { static constexpr bool value = false; };
+template <typename T> struct tail_line_sym<TailLineSymParams<T>> { static constexpr bool value = true; };
 
 BFSM_HD int mode_of(int i, int n) { return i < n / 2 ? i : i - n; }
 
@@ -1586,8 +1622,9 @@ BFSM_HD void body_gain_line_acc(const GainLineSumParams<T>& prm, Ctx& ctx) {
 // KN (Hermitian mode).  grid = (column blocks, 2 * directions of the chunk, batch).  One column = one (kind, j):
 // the 1-D inverse transform of the Nyquist row (kind 0: ly = -N/2, running over lz -> z) or column (kind 1:
 // lz = -N/2, running over ly -> y, corner excluded) of plane idx = N/2 + 1 + j, for the sign by & 1.
-template <int N, typename T, class Ctx>
-BFSM_HD void body_nyq_rows(const NyqRowsParams<T>& prm, Ctx& ctx) {
+// P = NyqRowsBiParams: the spectrum is chosen by the sign (workgroup-uniform).
+template <int N, typename T, class Ctx, class P>
+BFSM_HD void body_nyq_rows(const P& prm, Ctx& ctx) {
     constexpr int E = Wg<N>::E, TT = Wg<N>::T, NPL = Wg<N>::NPL, NQ = N / 2 - 1, H = N / 2;
     int p, u;
     lane_coords<NPL, Wg<N>::LROW>(ctx, p, u);
@@ -1603,7 +1640,9 @@ BFSM_HD void body_nyq_rows(const NyqRowsParams<T>& prm, Ctx& ctx) {
     const size_t b = (size_t)(prm.dir0 + dslot);
     const cx<T> px = prm.phx[b * N + idx];
     const cx<T> pyN = ctx.ldc(prm.phy + b * N + H), pzN = ctx.ldc(prm.phz + b * N + H);
-    const cx<T>* fh = prm.fhat + (size_t)ctx.bz() * N * N * N + (size_t)idx * N * N;
+    const cx<T>* spec = prm.fhat;
+    if constexpr (kn_bilinear<P>::value) { if (conj) spec = prm.fhat2; }
+    const cx<T>* fh = spec + (size_t)ctx.bz() * N * N * N + (size_t)idx * N * N;
     cx<T> v[E];
 #pragma unroll
     for (int m = 0; m < E; ++m) {
@@ -1657,6 +1696,21 @@ BFSM_HD void body_gain_inv_nyq(const GainInvNyqParams<T>& prm, Ctx& ctx) {
         const int kn = (ctx.by() - prm.ka_groups) * ctx.gx() + ctx.bx();
         if (kn >= prm.kn_blocks) return;
         const NyqRowsParams<T> pk{prm.ka.fhat, prm.r, prm.ka.phx, prm.ka.phy, prm.ka.phz, prm.ka.tw, prm.ka.dir0, prm.r_bstride};
+        GuestCtx<Ctx> g(ctx, 0, kn);
+        body_nyq_rows<N, T>(pk, g);
+        return;
+    }
+    body_gain_inv<N, T>(prm.ka, ctx);
+}
+// the same for the symmetric form: bilinear KA, KN reading its spectrum by sign
+template <int N, typename T, class Ctx>
+BFSM_HD void body_gain_inv_nyq(const GainInvNyqBiParams<T>& prm, Ctx& ctx) {
+    if (ctx.by() >= prm.ka_groups) {                                     // workgroup-uniform
+        const int kn = (ctx.by() - prm.ka_groups) * ctx.gx() + ctx.bx();
+        if (kn >= prm.kn_blocks) return;
+        NyqRowsBiParams<T> pk{};
+        static_cast<NyqRowsParams<T>&>(pk) = NyqRowsParams<T>{prm.ka.fhat, prm.r, prm.ka.phx, prm.ka.phy, prm.ka.phz, prm.ka.tw, prm.ka.dir0, prm.r_bstride};
+        pk.fhat2 = prm.ka.fhat2;
         GuestCtx<Ctx> g(ctx, 0, kn);
         body_nyq_rows<N, T>(pk, g);
         return;
@@ -2000,7 +2054,9 @@ BFSM_HD void body_tail_inv(const P& prm, Ctx& ctx) {
         for (int m = 0; m < E; ++m) {
             const int mz = mode_of(u + TT * m, N);
             const T b2 = prm.beta2[mx * mx + my * my + mz * mz];
-            const cx<T> t = prm.fhat[pbase + (u + TT * m) * N + p];
+            cx<T> t;                                // symmetric form: plane y == 2 reads the second loss spectrum
+            if constexpr (tail_inv_sym<P>::value) t = prm.fhat[(long long)(ctx.by() >> 1) * prm.fhat2_off + (long long)(pbase + (u + TT * m) * N + p)];
+            else t = prm.fhat[pbase + (u + TT * m) * N + p];
             v[m] = {b2 * t.x, b2 * t.y};
         }
     }
@@ -2008,6 +2064,8 @@ BFSM_HD void body_tail_inv(const P& prm, Ctx& ctx) {
     // (the loss plane is addressed as tg + tl_off: a select between the two pointers was lowered to an indexed load from a
     // private copy of the parameter block -- 24 bytes of scratch per lane in every instantiation)
     cx<T>* dst = prm.tg + (loss ? prm.tl_off : 0) + pbase;
+    if constexpr (tail_inv_sym<P>::value)             // three planes: 0, tl_off, tl2_off (arithmetic on y, no select)
+        dst = prm.tg + (long long)(ctx.by() & 1) * prm.tl_off + (long long)(ctx.by() >> 1) * prm.tl2_off + pbase;
 #pragma unroll
     for (int m = 0; m < E; ++m) dst[(u + TT * m) * N + p] = v[m];
 }
@@ -2029,7 +2087,27 @@ BFSM_HD void body_tail_line(const P& prm, Ctx& ctx) {
 #pragma unroll
     for (int m = 0; m < E; ++m) g[m] = prm.tg[base + (size_t)(u + TT * m) * N * N];
     fft_line_np<N, NPL, +1, T>(g, lds, p, u, twr, ctx);
-    if constexpr (tail_split<P>::value) {
+    if constexpr (tail_line_sym<P>::value) {
+        if (prm.with_loss) {
+            double q[E];
+#pragma unroll
+            for (int m = 0; m < E; ++m) l[m] = prm.tl[base + (size_t)(u + TT * m) * N * N];
+            fft_line_np<N, NPL, +1, T>(l, lds, p, u, twr, ctx);
+#pragma unroll
+            for (int m = 0; m < E; ++m) q[m] = (double)g[m].x - (double)l[m].x * prm.f[base + (size_t)(u + TT * m) * N * N];
+#pragma unroll
+            for (int m = 0; m < E; ++m) l[m] = prm.tl2[base + (size_t)(u + TT * m) * N * N];
+            fft_line_np<N, NPL, +1, T>(l, lds, p, u, twr, ctx);
+#pragma unroll
+            for (int m = 0; m < E; ++m) {
+                const size_t i = base + (size_t)(u + TT * m) * N * N;
+                prm.Q[i] = q[m] - (double)l[m].x * prm.f2[i];
+            }
+        } else {
+#pragma unroll
+            for (int m = 0; m < E; ++m) prm.Q[base + (size_t)(u + TT * m) * N * N] = (double)g[m].x;
+        }
+    } else if constexpr (tail_split<P>::value) {
 #pragma unroll
         for (int m = 0; m < E; ++m) l[m] = prm.tl[base + (size_t)(u + TT * m) * N * N];
         fft_line_np<N, NPL, +1, T>(l, lds, p, u, twr, ctx);

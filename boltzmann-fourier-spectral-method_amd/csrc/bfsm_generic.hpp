@@ -861,11 +861,25 @@ struct GenCombineSplitParams : GenCombineParams<T> {
 template <class P> struct gen_split { static constexpr bool value = false; };
 template <typename T> struct gen_split<GenCombineSplitParams<T>> { static constexpr bool value = true; };
 
+// Symmetric form Qs(g,f) (include/bfsm.h, bfsm_collide_symmetric*): Q = Re(gain) - Re(l) * f - Re(l2) * f2, two loss terms.
+// A parameter type of its own, launched under GK::Combine.
+template <typename T>
+struct GenCombineSymParams : GenCombineParams<T> {
+    const cx<T>* l2;
+    const double* f2;
+};
+template <class P> struct gen_sym { static constexpr bool value = false; };
+template <typename T> struct gen_sym<GenCombineSymParams<T>> { static constexpr bool value = true; };
+
 template <typename T, class Ctx, class P>
 BFSM_HD void body_gen_combine(const P& prm, Ctx& ctx) {
     const size_t idx = (size_t)ctx.bx() * ctx.nthreads() + ctx.tid();
     if (idx >= prm.G) return;
-    if constexpr (gen_split<P>::value) {
+    if constexpr (gen_sym<P>::value) {
+        double q = (double)prm.g[idx].x;
+        if (prm.with_loss) q = q - (double)prm.l[idx].x * prm.f[idx] - (double)prm.l2[idx].x * prm.f2[idx];
+        prm.Q[idx] = q;
+    } else if constexpr (gen_split<P>::value) {
         prm.Q[idx] = (double)prm.g[idx].x;
         prm.nu[idx] = (double)prm.l[idx].x;
     } else {
@@ -1235,7 +1249,7 @@ struct GenericPipeline : DeviceBuffers<Backend> {
     }
     // elements between the scratch of two batch members
     size_t a_mstride() const { return (size_t)2 * chunk * G; }
-    void gain_chunk_fused(const Chunk& c, bool first, int nb = 1, const cx<T>* fb = nullptr) {
+    void gain_chunk_fused(const Chunk& c, bool first, int nb, const cx<T>* fb, const cx<T>* fa) {
         const double Gc = (double)G * sizeof(cx<T>);
         // A1', A2' = IFFT_yz(alpha f_hat / G), IFFT_yz(conj(alpha) f_hat / G), straight from f_hat (x stays spectral)
         be->mark(BFSM_K_GAIN_INV, 2.0 * c.n * nb * Gc);
@@ -1247,8 +1261,8 @@ struct GenericPipeline : DeviceBuffers<Backend> {
         // 0.117 -> 0.133 ms there) -- profiles/r04_generic_fused_ab.txt
         constexpr bool PAIR = sizeof(T) == 8;
 #endif
-        if (PAIR) plane<GK::PlanePair>(step(fhat, a, c.n * nb, +1).load(GEN_PHASE, fb).from(c.dir0).strides(0, 0).members(c.n, G, a_mstride()));
-        else plane<GK::Plane>(step(fhat, a, 2 * c.n * nb, +1).load(GEN_PHASE, fb).from(c.dir0).strides(0, G).members(2 * c.n, G, a_mstride()));
+        if (PAIR) plane<GK::PlanePair>(step(fa, a, c.n * nb, +1).load(GEN_PHASE, fb).from(c.dir0).strides(0, 0).members(c.n, G, a_mstride()));
+        else plane<GK::Plane>(step(fa, a, 2 * c.n * nb, +1).load(GEN_PHASE, fb).from(c.dir0).strides(0, G).members(2 * c.n, G, a_mstride()));
         line3(c, nb);
         GenPlaneAccParams<T> kp{};
         const int groups = groups_for(c.n);
@@ -1291,12 +1305,47 @@ struct GenericPipeline : DeviceBuffers<Backend> {
         finish(Q_dev, g_dev, with_loss, 1, false, fb, nu_dev);
     }
 
-    // the gain term of this shard from fhat (and fb: the conj(alpha) operand of the bilinear form) into qhat
-    void gain_spectra(int nb, const cx<T>* fb) {
+    // Symmetric form Qs(g,f) = Q(g,f) + Q(f,g) (bfsm_collide_symmetric*): the bilinear gain launches twice, the second pass
+    // with the spectra exchanged and accumulating onto the first pass's qhat (fixed order); then one tail with both loss
+    // terms: gain and beta2 f_hat through the launches of finish, beta2 g_hat into the (free) A1 / A2 scratch, one combine.
+    void collide_symmetric(double* Q_dev, const double* g_dev, const double* f_dev, bool with_loss) {
         const double Gc = (double)G * sizeof(cx<T>);
-        bool first = true;
+        spectrum(g_dev, fhat, 1);
+        const cx<T>* fb = fhat;
+        if (f_dev != g_dev) { spectrum(f_dev, fhat_b(), 1); fb = fhat_b(); }
+        gain_spectra(1, fb);
+        gain_spectra(1, fhat, fb, true);
+        cx<T>* tg = tail;
+        cx<T>* tl = tail + (size_t)max_batch * G;
+        cx<T>* tl2 = a;
+        be->mark(BFSM_K_TAIL, (with_loss ? 10.5 : 3.5) * Gc);
+        if (with_loss) {
+            const size_t half = (size_t)max_batch * G;
+            fft(step(qhat, tail, 2, +1).along(0).load(GEN_TAIL2, fb).strides(0, half).members(2, G, G));
+            be->mark(BFSM_K_TAIL, 0);
+            fft(step(tail, tail, 2, +1).members(1, half, half).marks(BFSM_K_TAIL));
+            be->mark(BFSM_K_TAIL, 0);
+            fft(step(fhat, tl2, 1, +1).along(0).load(GEN_BETA2));
+            be->mark(BFSM_K_TAIL, 0);
+            fft(step(tl2, tl2, 1, +1).marks(BFSM_K_TAIL));
+        } else {
+            fft(step(qhat, tg, 1, +1).along(0));
+            be->mark(BFSM_K_TAIL, 0);
+            fft(step(tg, tg, 1, +1).marks(BFSM_K_TAIL));
+        }
+        GenCombineSymParams<T> kc{{tg, tl, g_dev, Q_dev, G, with_loss ? 1 : 0}, tl2, f_dev};
+        be->mark(BFSM_K_TAIL, 0);
+        be->template launch_gen<GK::Combine, T>((int)((G + GEN_THREADS - 1) / GEN_THREADS), 1, GEN_THREADS, 0, kc);
+    }
+
+    // the gain term of this shard from fhat (and fb: the conj(alpha) operand of the bilinear form) into qhat.
+    // fa (symmetric form): the alpha operand's spectrum instead of fhat; add: accumulate onto the qhat of an earlier pass
+    void gain_spectra(int nb, const cx<T>* fb, const cx<T>* fa = nullptr, bool add = false) {
+        const double Gc = (double)G * sizeof(cx<T>);
+        if (!fa) fa = fhat;
+        bool first = !add;
         for (const Chunk& c : plan.chunks) {
-            if (route.seq == GenSeq::Fused) { gain_chunk_fused(c, first, nb, fb); first = false; continue; }
+            if (route.seq == GenSeq::Fused) { gain_chunk_fused(c, first, nb, fb, fa); first = false; continue; }
             // A1, A2 = IFFT(alpha f_hat / G), IFFT(conj(alpha) f_hat / G): members 2d, 2d + 1 of `a` (phase factors on the
             // load side, straight from f_hat); P_hat = FFT(A1 * A2) over A1 (members 2d, stride 2G)
             // accounting: the SURVEY 8(d) model attributes 2 array passes per direction to the inverse transforms, 3 to the
@@ -1305,12 +1354,12 @@ struct GenericPipeline : DeviceBuffers<Backend> {
             if (route.seq == GenSeq::Line3) {
                 // the (y,z) passes of the inverse transforms first, then the x-line kernel, then the (y,z) passes of the forward
                 // transform: 14 array moves (8 with the plane kernel).  Its axis passes run z before y backward, y before z forward
-                fft(step(fhat, a, 2 * c.n, +1).load(GEN_PHASE, fb).strides(0, G).from(c.dir0).marks(BFSM_K_GAIN_INV).swapped());
+                fft(step(fa, a, 2 * c.n, +1).load(GEN_PHASE, fb).strides(0, G).from(c.dir0).marks(BFSM_K_GAIN_INV).swapped());
                 line3(c);
                 be->mark(BFSM_K_GAIN_LINE, 0);
                 fft(step(a, a, c.n, -1).strides(2 * G, 2 * G).marks(BFSM_K_GAIN_LINE).swapped());
             } else {
-                fft(step(fhat, a, 2 * c.n, +1).along(0).load(GEN_PHASE, fb).strides(0, G).from(c.dir0));
+                fft(step(fa, a, 2 * c.n, +1).along(0).load(GEN_PHASE, fb).strides(0, G).from(c.dir0));
                 be->mark(BFSM_K_GAIN_INV, 0);
                 fft(step(a, a, 2 * c.n, +1).marks(BFSM_K_GAIN_INV));
                 // the product is formed on the load side of the first forward pass, then transformed in place
@@ -1323,7 +1372,7 @@ struct GenericPipeline : DeviceBuffers<Backend> {
             accumulate(a, 2 * G, c.n, c.dir0, first, true);
             first = false;
         }
-        if (first) {   // empty shard: qhat = 0
+        if (first && !add) {   // empty shard: qhat = 0
             be->mark(-1, 0);
             accumulate(a, 2 * G, 0, 0, true, true, nb, 0, G);
         }

@@ -828,6 +828,41 @@ int bfsm_collide_bilinear(bfsm_handle h, double* Q_dev, const double* g_dev, con
     return bfsm_synchronize(h);
 }
 
+// Symmetric form Qs(g,f) = Q(g,f) + Q(f,g) on every kind of handle (bfsm_calls.hpp, collide_symmetric): both operand orders of
+// every direction, so the antipodal merge of the exact modes needs no g = f.
+int bfsm_collide_symmetric_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, int with_loss,
+                                         void* stream) {
+    if (!h) return BFSM_ERR_INVALID;
+    BFSM_GUARDED(h,
+        DeviceGuard guard(h->desc.device);
+        int rc = enter(h, guard, stream);
+        if (rc) return rc;
+        if (!g_dev || !f_dev || !Q_dev) return fail(h, BFSM_ERR_INVALID, "null Q, g or f");
+        const double* q0 = Q_dev;
+        const double* q1 = Q_dev + h->G;
+        auto overlaps = [&](const double* a) { return a < q1 && q0 < a + h->G; };
+        if (overlaps(g_dev) || overlaps(f_dev)) return fail(h, BFSM_ERR_INVALID, "Q must not overlap g or f");
+        if (conserving(h) && (rc = check_cons_q(h, Q_dev))) return rc;
+        h->be.begin_eval();
+        h->with([&](auto& p) { bfsm::collide_symmetric(p, Q_dev, g_dev, f_dev, with_loss != 0); });
+        if (conserving(h)) h->cons->apply(Q_dev, 1);
+        return leave(h, "bfsm_collide_symmetric");
+    )
+}
+
+int bfsm_collide_symmetric_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, void* stream) {
+    if (!h) return BFSM_ERR_INVALID;
+    if (!h->full_shard)
+        return fail(h, BFSM_ERR_INVALID, "bfsm_collide_symmetric needs a handle that owns all directions; use bfsm_collide_symmetric_partial_async + a sum over the ranks");
+    return bfsm_collide_symmetric_partial_async(h, Q_dev, g_dev, f_dev, 1, stream);
+}
+
+int bfsm_collide_symmetric(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev) {
+    int rc = bfsm_collide_symmetric_async(h, Q_dev, g_dev, f_dev, nullptr);
+    if (rc) return rc;
+    return bfsm_synchronize(h);
+}
+
 // Gain / loss split: the sequences of bfsm_collide_batch_partial_async / bfsm_collide_bilinear_partial_async with the two terms
 // of the tail kept apart (Pipeline::finish / GenericPipeline::finish with nu_dev).  N = 16 takes the plane-tile pipeline.  No
 // projection: BFSM_FLAG_CONSERVE applies to Q, not to its parts.

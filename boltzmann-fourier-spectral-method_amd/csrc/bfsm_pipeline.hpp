@@ -428,6 +428,9 @@ struct Pipeline : DeviceBuffers<Backend> {
     cx<T>* pseg = nullptr;        // [segment][x][y][z]
     Segment* segs_unit = nullptr; // one single-slot segment per pseg entry, same r
     T* ones = nullptr;
+    cx<T>* slab_sym = nullptr;    // symmetric form: [2 slab_count] slabs and segment sums, the second loss array of its tail
+    cx<T>* pseg_sym = nullptr;
+    cx<T>* tl_sym = nullptr;
     cx<T>* rnyq = nullptr;        // Hermitian mode: Nyquist rows [slot][sign][kind][N/2-1][N]
     size_t slab_count = 0;
     // N = 16 whole-direction path: one partial Q_hat per workgroup
@@ -473,12 +476,16 @@ struct Pipeline : DeviceBuffers<Backend> {
             pp = a1;
         }
         if (plan.hermitian) ok = ok && dev_alloc(rnyq, nb * cap * r_per_dir());
+        // the symmetric form Qs(g,f) runs two gain passes per chunk, the second into segment sums and slabs of its own: the
+        // segment tables twice over (entry slab_count + i = entry i), and buffers of its own at the end of init
+        std::vector<Segment> segs2(plan.segs);
+        segs2.insert(segs2.end(), plan.segs.begin(), plan.segs.end());
         ok = ok && dev_alloc(slab, nb * nslab * G);
         ok = ok && dev_copy(tw, t.tw) && dev_copy(phx, t.phx) && dev_copy(phy, t.phy) && dev_copy(phz, t.phz);
-        ok = ok && dev_copy(dirw, t.dirw) && dev_copy(beta1, t.beta1) && dev_copy(beta2, t.beta2) && dev_copy(segs, plan.segs);
+        ok = ok && dev_copy(dirw, t.dirw) && dev_copy(beta1, t.beta1) && dev_copy(beta2, t.beta2) && dev_copy(segs, segs2);
         if (ok && segment_sums()) {
-            std::vector<Segment> unit(plan.segs.size());
-            for (size_t i = 0; i < unit.size(); ++i) unit[i] = Segment{(int)i, 1, plan.segs[i].r, 0};
+            std::vector<Segment> unit(segs2.size());
+            for (size_t i = 0; i < unit.size(); ++i) unit[i] = Segment{(int)i, 1, segs2[i].r, 0};
             std::vector<T> one(unit.size() ? unit.size() : 1, (T)1);
             ok = ok && dev_alloc(pseg, nb * nslab * G);
             ok = ok && dev_copy(segs_unit, unit) && dev_copy(ones, one);
@@ -492,6 +499,11 @@ struct Pipeline : DeviceBuffers<Backend> {
             small_wgs = (int)((nd + small_per - 1) / small_per);
             ok = ok && dev_alloc(small_part, (size_t)(small_wgs + 1) * G);
         }
+        // Scratch of the symmetric form alone, allocated last so that every buffer of the other entry points is made in the order
+        // and size it always was: 2 x slab_count slabs and segment sums of one distribution, and the second loss array
+        ok = ok && dev_alloc(slab_sym, 2 * nslab * G);
+        if (segment_sums()) ok = ok && dev_alloc(pseg_sym, 2 * nslab * G);
+        ok = ok && dev_alloc(tl_sym, G);
         if (!ok) { err = "device allocation failed"; return BFSM_ERR_NOMEM; }
         return BFSM_OK;
     }
@@ -572,15 +584,50 @@ struct Pipeline : DeviceBuffers<Backend> {
         finish(Q_dev, g_dev, with_loss, 1, fu, fhat_b(), nu_dev);
     }
 
-    // The gain term of this shard from the spectra in fhat (and fhat2 for the bilinear form: the conj(alpha) operand) into qhat
-    void gain_spectra(int nb, bool do_reduce, const cx<T>* fhat2) {
+    // Symmetric form Qs(g,f) = Q(g,f) + Q(f,g) (include/bfsm.h, bfsm_collide_symmetric*), every mode.  g_hat in fhat, f_hat in
+    // fhat + G; per chunk two gain passes with the spectra exchanged (gain_spectra, symmetric); one KC, one reduce (fused into
+    // the tail when the 2 x slab_count slabs are at most 8), one tail with both loss terms.  On a merged plan (exact
+    // reductions, antipodal rule) the two passes per effective direction s < M/2 are P_s(g,f) and P_s(f,g) = P_{s+M/2}(g,f)
+    // with the doubled weight: the whole symmetric gain from M/2 directions.  On every other plan they are the two gains.
+    bool fuse_reduce_symmetric() const { return 2 * slab_count <= 8; }
+    void collide_symmetric(double* Q_dev, const double* g_dev, const double* f_dev, bool with_loss) {
+        spectrum(g_dev, fhat, 1);
+        const cx<T>* fb = fhat;                                   // g == f: one transform, both operands read the same spectrum
+        if (f_dev != g_dev) { spectrum(f_dev, fhat_b(), 1); fb = fhat_b(); }
+        const bool fu = fuse_reduce_symmetric();
+        gain_spectra(1, !fu, fb, true);
+        const int N = plan.N;
+        const double Gc = (double)plan.G() * cbytes();
+        const size_t n_slabs = 2 * slab_count, s_bs = (slab_count ? slab_count : 1) * plan.G();
+        // tail: gain plane, beta2 f_hat (multiplied by g), beta2 g_hat (multiplied by f)
+        TailInvSymParams<T> ta{{qhat, fb, beta2, tg, (long long)(tl - tg), tw, slab_sym, beta1, segs, fu ? (int)n_slabs : -1, plan.n2stride, s_bs},
+                               (long long)(fhat - fb), (long long)(tl_sym - tg)};
+        be->mark(BFSM_K_TAIL, ((with_loss ? 6.0 : 2.0) + (fu ? (double)n_slabs - 1.0 : 0.0)) * Gc);
+        be->template launch<K::TailInv, T>(N, with_loss ? 3 : 1, 1, ta, N);
+        TailLineSymParams<T> tb{{tg, tl, g_dev, Q_dev, tw, with_loss ? 1 : 0}, tl_sym, f_dev};
+        be->mark(BFSM_K_TAIL, (with_loss ? 5.0 : 1.5) * Gc);
+        be->template launch<K::TailLine, T>(line_blocks(), 1, 1, tb, N);
+    }
+
+    // The gain term of this shard from the spectra in fhat (and fhat2 for the bilinear form: the conj(alpha) operand) into qhat.
+    // symmetric (one distribution, fhat2 given): every chunk runs a second pass with the two spectra exchanged, whose segment
+    // sums and slabs are the entries slab_count + i of slab_sym / pseg_sym; KC, the reduce and the fused tail then cover 2 x slab_count entries, so
+    // qhat = gain_hat[g,f] + gain_hat[f,g] in one fixed order.
+    void gain_spectra(int nb, bool do_reduce, const cx<T>* fhat2, bool symmetric = false) {
         const int N = plan.N;
         const double Gc = (double)plan.G() * cbytes() * nb;
         const size_t G = plan.G();
         const size_t a_bs = cap * (size_t)a_planes * N * N, s_bs = (slab_count ? slab_count : 1) * G;
         const size_t r_bs = cap * r_per_dir();
         const double hfrac = (double)a_planes / N;                 // share of A' actually stored
-        for (const Chunk& c : plan.chunks) {
+        const int n_pass = symmetric ? 2 : 1;
+        cx<T>* const slab = symmetric ? slab_sym : this->slab;       // the symmetric form's own slabs and segment sums
+        cx<T>* const pseg = symmetric ? pseg_sym : this->pseg;
+        const size_t n_slabs = slab_count * (size_t)n_pass;
+        for (const Chunk& c : plan.chunks) for (int pass = 0; pass < n_pass; ++pass) {
+            const cx<T>* fa = pass ? fhat2 : fhat;               // the alpha operand's spectrum
+            const cx<T>* fb = pass ? fhat : fhat2;               // the conj(alpha) operand's (null: Q(f,f))
+            const int seg0 = c.seg0 + pass * (int)slab_count;
             // KA's parallelism is planes x direction groups: keep >= 2 workgroups per CU when only N/2 + 1 planes run
             const int tw_ = target_workgroups(N, max_batch);
             // one resident wave of workgroups, except at N = 64: two rounds of half-length workgroups let the CUs that
@@ -600,13 +647,17 @@ struct Pipeline : DeviceBuffers<Backend> {
             // Hermitian mode, N = 64: the chunk's 2 c.n Nyquist-row workgroups (KN) ride along as extra rows of KA's grid
             const bool kn_rides = plan.hermitian && kn_rides_along(N);
             const int kn_blocks = kn_rides ? 2 * c.n : 0, kn_rows = (kn_blocks + a_planes - 1) / a_planes;
-            GainInvParams<T> ka{fhat, a1, a2, phx, phy, phz, tw, c.dir0, c.n, per_group_a, a_bs, a_planes, warm ? 1 : 0};
+            GainInvParams<T> ka{fa, a1, a2, phx, phy, phz, tw, c.dir0, c.n, per_group_a, a_bs, a_planes, warm ? 1 : 0};
             be->mark(BFSM_K_GAIN_INV, 2.0 * c.n * Gc * hfrac);
-            if (fhat2) {                        // bilinear form (faithful mode only: no Nyquist rows, no GainInvTwo)
+            if (fb) {                           // two operands: Q(g,f) on faithful handles, Qs(g,f) on every mode
                 GainInvBiParams<T> kab{};
                 static_cast<GainInvParams<T>&>(kab) = ka;
-                kab.fhat2 = fhat2;
-                be->template launch<K::GainInv, T>(a_planes, ga, nb, kab, N);
+                kab.fhat2 = fb;
+                if (kn_rides) {
+                    GainInvNyqBiParams<T> kan{kab, rnyq, r_bs, kn_blocks, ga};
+                    be->template launch<K::GainInvNyq, T>(a_planes, ga + kn_rows, nb, kan, N);
+                } else if (pair_geometry() && !interleaved()) be->template launch<K::GainInvTwo, T>(a_planes, ga, nb, kab, N);
+                else be->template launch<K::GainInv, T>(a_planes, ga, nb, kab, N);
             } else if (kn_rides) {              // KA + guest KN workgroups
                 GainInvNyqParams<T> kan{ka, rnyq, r_bs, kn_blocks, ga};
                 be->template launch<K::GainInvNyq, T>(a_planes, ga + kn_rows, nb, kan, N);
@@ -614,7 +665,7 @@ struct Pipeline : DeviceBuffers<Backend> {
             else be->template launch<K::GainInv, T>(a_planes, ga, nb, ka, N);
             if (!plan.exact_reductions && segment_sums()) {
                 // faithful mode: every direction's own forward x transform, the segment sum of P' in registers
-                GainLineSumParams<T> kb{{a1, a2, pseg, dirw, segs, tw, c.dir0, c.seg0, a_bs, s_bs}};
+                GainLineSumParams<T> kb{{a1, a2, pseg, dirw, segs, tw, c.dir0, seg0, a_bs, s_bs}};
                 be->mark(BFSM_K_GAIN_LINE, (2.0 * c.n + c.n_seg) * Gc);
                 be->template launch<K::GainLineAcc, T>(line_blocks(), c.n_seg, nb, kb, N);
             } else if (!plan.exact_reductions) {
@@ -622,33 +673,38 @@ struct Pipeline : DeviceBuffers<Backend> {
                 GainLineParams<T> kb{a1, a2, tw, a_bs, pp, p_bs};
                 be->mark(BFSM_K_GAIN_LINE, 3.0 * c.n * Gc);
                 be->template launch<K::GainLine, T>(line_blocks(), c.n, nb, kb, N);
-                GainFwdParams<T> kc{pp, slab, dirw, segs, tw, c.dir0, c.seg0, p_bs, s_bs};
+                GainFwdParams<T> kc{pp, slab, dirw, segs, tw, c.dir0, seg0, p_bs, s_bs};
                 be->mark(BFSM_K_GAIN_FWD, 1.0 * c.n * Gc);
                 be->template launch<K::GainFwd, T>(N, c.n_seg, nb, kc, N);
             } else if (!plan.hermitian) {
-                GainLineAccParams<T> kb{a1, a2, pseg, dirw, segs, tw, c.dir0, c.seg0, a_bs, s_bs};
+                GainLineAccParams<T> kb{a1, a2, pseg, dirw, segs, tw, c.dir0, seg0, a_bs, s_bs};
                 be->mark(BFSM_K_GAIN_LINE, (2.0 * c.n + c.n_seg) * Gc);
                 be->template launch<K::GainLineAcc, T>(line_blocks(), c.n_seg, nb, kb, N);
             } else {
                 if (!kn_rides) {
-                    NyqRowsParams<T> kn{fhat, rnyq, phx, phy, phz, tw, c.dir0, r_bs};
+                    NyqRowsParams<T> kn{fa, rnyq, phx, phy, phz, tw, c.dir0, r_bs};
                     const int npl = line_npl(N), ncol = 2 * (N / 2 - 1);
                     be->mark(BFSM_K_GAIN_INV, 0.0);
-                    be->template launch<K::NyqRows, T>((ncol + npl - 1) / npl, 2 * c.n, nb, kn, N);
+                    if (fb) {
+                        NyqRowsBiParams<T> knb{};
+                        static_cast<NyqRowsParams<T>&>(knb) = kn;
+                        knb.fhat2 = fb;
+                        be->template launch<K::NyqRows, T>((ncol + npl - 1) / npl, 2 * c.n, nb, knb, N);
+                    } else be->template launch<K::NyqRows, T>((ncol + npl - 1) / npl, 2 * c.n, nb, kn, N);
                 }
-                GainLineAccHParams<T> kb{a1, a2, rnyq, pseg, dirw, segs, tw, c.dir0, c.seg0, a_bs, s_bs, r_bs};
+                GainLineAccHParams<T> kb{a1, a2, rnyq, pseg, dirw, segs, tw, c.dir0, seg0, a_bs, s_bs, r_bs};
                 be->mark(BFSM_K_GAIN_LINE, (2.0 * c.n * hfrac + c.n_seg) * Gc);
                 be->template launch<K::GainLineAccH, T>(line_blocks(), c.n_seg, nb, kb, N);
             }
         }
         if (segment_sums() && slab_count) {   // one forward tile pass per segment, all chunks at once
             GainFwdParams<T> kc{pseg, slab, ones, segs_unit, tw, 0, 0, s_bs, s_bs};
-            be->mark(BFSM_K_GAIN_FWD, 1.0 * (double)slab_count * Gc);
-            be->template launch<K::GainFwd, T>(N, (int)slab_count, nb, kc, N);
+            be->mark(BFSM_K_GAIN_FWD, 1.0 * (double)n_slabs * Gc);
+            be->template launch<K::GainFwd, T>(N, (int)n_slabs, nb, kc, N);
         }
         if (do_reduce) {
-            ReduceParams<T> kr{slab, qhat, beta1, segs, (int)slab_count, plan.n2stride, s_bs};
-            be->mark(BFSM_K_REDUCE, ((double)slab_count + 1.0) * Gc);
+            ReduceParams<T> kr{slab, qhat, beta1, segs, (int)n_slabs, plan.n2stride, s_bs};
+            be->mark(BFSM_K_REDUCE, ((double)n_slabs + 1.0) * Gc);
             be->template launch<K::Reduce, T>((int)((plan.G() + 255) / 256), nb, 1, kr, N);
         }
     }

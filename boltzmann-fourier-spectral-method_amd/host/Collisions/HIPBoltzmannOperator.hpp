@@ -51,6 +51,9 @@ public:
     // Bilinear form Q(g,f) (include/bfsm.h, bfsm_collide_bilinear): device pointers, blocking.  Not part of
     // AbstractCollisionOperator; Q(f,f) is computeCollision(Q, f).
     void computeCollision(double* Q, const double* g, const double* f);
+    // Symmetric form Qs(g,f) = Q(g,f) + Q(f,g) (include/bfsm.h, bfsm_collide_symmetric): device pointers, blocking; served by
+    // every handle, the exact and Hermitian modes included.  L_f[h] = Qs(f,h).
+    void computeSymmetricCollision(double* Q, const double* g, const double* f);
 
     // Gain / loss split (include/bfsm.h, bfsm_collide_split): Qgain = Q+(f,f), nu = the collision frequency nu[f], so that
     // Q = Qgain - f * nu; device pointers, blocking.  lossRate: nu alone, without any gain work (blocking).

@@ -47,6 +47,10 @@ void BoltzmannOperator<HIP_Backend>::computeCollision(double* Q, const double* g
     check(bfsm_collide_bilinear(handle_, Q, g, f), "computeCollision (bilinear)");
 }
 
+void BoltzmannOperator<HIP_Backend>::computeSymmetricCollision(double* Q, const double* g, const double* f) {
+    check(bfsm_collide_symmetric(handle_, Q, g, f), "computeSymmetricCollision");
+}
+
 void BoltzmannOperator<HIP_Backend>::computeCollisionSplit(double* Qgain, double* nu, const double* f_in) {
     check(bfsm_collide_split(handle_, Qgain, nu, f_in), "computeCollisionSplit");
 }

@@ -79,7 +79,7 @@ enum {
     BFSM_FLAG_NO_SMALL_PATH = 8,
     /* Conservative spectral method (Gamba & Tharkabhushanam, J. Comput. Phys. 2009; new functionality, INTEGRATION.md
      * section 6): every entry point that writes Q writes PQ instead -- bfsm_collide*, bfsm_collide_batch*, bfsm_finish,
-     * bfsm_finish_partial, bfsm_collide_partial_async, bfsm_collide_batch_partial_async and bfsm_collide_bilinear*.  P is the
+     * bfsm_finish_partial, bfsm_collide_partial_async, bfsm_collide_batch_partial_async, bfsm_collide_bilinear* and bfsm_collide_symmetric*.  P is the
      * L2-orthogonal projection onto the grid functions with zero discrete mass, momentum and energy:
      *     PQ = Q - sum_k (<psi_k, Q> / <psi_k, psi_k>) psi_k,   psi = {1, vx, vy, vz, |v|^2 - c},  c = mean of |v|^2 over the grid,
      * <a,b> = sum over the G grid points (the grid is symmetric on every axis, so the basis is orthogonal).  P is fixed and
@@ -226,6 +226,44 @@ int bfsm_collide_bilinear(bfsm_handle h, double* Q_dev, const double* g_dev, con
 int bfsm_collide_bilinear_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, void* stream);
 int bfsm_collide_bilinear_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev,
                                         int with_loss, void* stream);
+
+/*
+ * Symmetric bilinear form (new functionality; the presence of these symbols is the capability check, BFSM_VERSION stays 2):
+ *     Qs(g,f) = Q(g,f) + Q(f,g) = Re IFFT(Q_gain_hat[g_hat, f_hat] + Q_gain_hat[f_hat, g_hat]) - g * nu[f] - f * nu[g],
+ * with Q(.,.) as above and nu[f] = Re IFFT(beta2 f_hat / G); the definition holds for any rule.  L_f[h] = Qs(f,h) and
+ * Qs(f,f) = 2 Q(f,f).  Unlike Q(g,f) alone it is served by EVERY handle, the exact and Hermitian modes included: with
+ * P_s(g,f) = IFFT(alpha_s g_hat) * IFFT(conj(alpha_s) f_hat) and alpha_{-sigma} = conj(alpha_sigma), P_{-sigma}(g,f) = P_sigma(f,g),
+ * so on a rule with sigma_{s+M/2} == -sigma_s and equal weights (verified bit-exactly at bfsm_create)
+ *     gain(g,f) + gain(f,g) = sum_{s < M/2} 2 w_s [P_s(g,f) + P_s(f,g)]:
+ * the merged plan (M/2 directions, doubled weights) applied to both operand orders.  Both operand orders are computed for
+ * every direction on every handle, so rules without that symmetry are served as well (unmerged, every direction twice).
+ *   - g, f, Q: device pointers to one distribution each; a handle created with max_batch > 1 serves a single call.  g == f
+ *     (the same pointer) is allowed; Q must not overlap g or f (BFSM_ERR_INVALID); a null pointer gives BFSM_ERR_INVALID.
+ *   - routes.  Fused cubes, every mode and both precisions: per chunk two passes of the gain kernels with the spectra
+ *     exchanged -- KA (the bilinear operand selection, in the Hermitian mode with planes = N/2 + 1, its two-array form at
+ *     N = 128 fp32 and its Nyquist-row guests at N = 64), the mode's own x-line kernel -- the second pass into segment sums
+ *     and slabs of its own (buffers of this call alone, 2 x the plan's slabs, reserved at create); then ONE forward-tile pass, ONE reduce (fused into the
+ *     tail when there are at most 8 slabs in all) and ONE tail with a third plane (beta2 g_hat) and the combine
+ *     Q = gain - g nu[f] - f nu[g].  Four stored A' arrays per effective direction, written once and read once; fixed-order
+ *     sums, no atomics, bitwise reproducible.  No geometry stores all N planes: the Hermitian saving applies everywhere.
+ *     N = 16 takes the plane-tile pipeline, as for the bilinear form.  Size-generic boxes: the bilinear gain launches twice,
+ *     the second pass accumulating onto the first one's Q_hat, then one tail with both loss terms (a second loss array in the
+ *     idle A1 / A2 scratch, one combine kernel).
+ *   - bfsm_collide_symmetric is blocking; _async enqueues on `stream`; both need a handle that owns all directions.
+ *     _partial_async works on a direction shard: Q = Re IFFT(this shard's share of the symmetric gain) [- g nu[f] - f nu[g] if
+ *     with_loss]; the caller sums Q over the ranks, exactly one rank passing with_loss != 0.  On merged handles the shard
+ *     maps to effective directions exactly as for Q(f,f).
+ *   - BFSM_FLAG_CONSERVE: Q := P Qs, applied once (Q 16-byte aligned, as on the other entry points).  P Qs(f,h) is exactly the
+ *     Jacobian of P o Q at f applied to h.
+ *   - the _async forms are allocation-free after bfsm_create, graph-capturable after one evaluation outside a capture and
+ *     tracked by bfsm_synchronize.  With BFSM_FLAG_PROFILE the counters' kernel_launches / kernel_ms / kernel_alg_bytes cover
+ *     the sequence (byte model: symmetric_moved_bytes_per_eval in csrc/bfsm_calls.hpp).
+ *   - bfsm_collide_bilinear* and bfsm_collide_bilinear_split* are unchanged: BFSM_ERR_UNSUPPORTED on exact-reduction handles.
+ */
+int bfsm_collide_symmetric(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev);
+int bfsm_collide_symmetric_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, void* stream);
+int bfsm_collide_symmetric_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev,
+                                         int with_loss, void* stream);
 
 /*
  * Gain / loss split (new functionality; the presence of these symbols is the capability check, BFSM_VERSION stays 2).
