@@ -27,7 +27,10 @@ EXPORTED_SYMBOLS = (
     "bfsm_collide_bilinear_split_partial_async", "bfsm_loss_rate_async",
     "bfsm_moments_async", "bfsm_maxwellian_async",
     "bfsm_collide_symmetric", "bfsm_collide_symmetric_async", "bfsm_collide_symmetric_partial_async",
+    "bfsm_collide_symmetric_batch", "bfsm_collide_symmetric_batch_partial_async", "bfsm_collide_bilinear_batch_partial_async",
 )
+# the share argument of the batched two-operand forms (include/bfsm.h: BFSM_SHARE_*), by the name the Python binding takes
+SHARE = {None: 0, "g": 1, "f": 2}
 
 _dp = ctypes.POINTER(ctypes.c_double)
 
@@ -121,7 +124,10 @@ def load_library(path=None):
                        ("bfsm_moments_async", [vp, vp, vp, ctypes.c_int, vp]),
                        ("bfsm_maxwellian_async", [vp, vp, vp, ctypes.c_int, vp]),
                        ("bfsm_collide_symmetric", [vp, vp, vp, vp]), ("bfsm_collide_symmetric_async", [vp, vp, vp, vp, vp]),
-                       ("bfsm_collide_symmetric_partial_async", [vp, vp, vp, vp, ctypes.c_int, vp])):
+                       ("bfsm_collide_symmetric_partial_async", [vp, vp, vp, vp, ctypes.c_int, vp]),
+                       ("bfsm_collide_symmetric_batch", [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int]),
+                       ("bfsm_collide_symmetric_batch_partial_async", [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]),
+                       ("bfsm_collide_bilinear_batch_partial_async", [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp])):
         if hasattr(L, name):
             fn = getattr(L, name)
             fn.argtypes = args

@@ -209,6 +209,40 @@ class HIPBoltzmannOperator:
                     and t.numel() == int(n_batch) * G):
                 raise ValueError("arguments must be contiguous float64 CUDA tensors with n_batch*Nvx*Nvy*Nvz elements")
 
+    # Batched two-operand forms (include/bfsm.h, bfsm_collide_symmetric_batch*, bfsm_collide_bilinear_batch_partial_async): member i
+    # of Q = Qs(g_i, f_i) or Q(g_i, f_i) for n_batch <= max_batch pairs in one launch sequence.  share: None, "g" or "f" -- that
+    # operand is ONE distribution (G elements) every member uses, transformed once.
+    def _require_pairs(self, Q, g, f, n_batch, share):
+        if share not in capi.SHARE:
+            raise ValueError('share must be None, "g" or "f"')
+        self._require_batch(n_batch, Q)
+        self._require_batch(1 if share == "g" else n_batch, g)
+        self._require_batch(1 if share == "f" else n_batch, f)
+        return capi.SHARE[share]
+
+    def computeSymmetricCollisionBatch(self, Q, g, f, n_batch, share=None, stream=None):
+        """Q[i] = Qs(g_i, f_i); needs a handle that owns all directions.  stream=None: blocking; otherwise enqueued on it."""
+        sh = self._require_pairs(Q, g, f, n_batch, share)
+        if stream is None:
+            self._check(self._lib.bfsm_collide_symmetric_batch(self._h, _ptr(Q), _ptr(g), _ptr(f), int(n_batch), sh))
+            return
+        n_dirs = self.gl_quadrature.getNumberOfPoints() * self.spherical_quadrature.getNumberOfPoints()
+        if self._dir_range not in ((0, 0), (0, n_dirs)):
+            raise ValueError("computeSymmetricCollisionBatch needs a handle that owns all directions; use collideSymmetricBatchPartial")
+        self.collideSymmetricBatchPartial(Q, g, f, n_batch, True, share, stream)
+
+    def collideSymmetricBatchPartial(self, Q, g, f, n_batch, with_loss, share=None, stream=0):
+        """This shard's part of Qs(g_i, f_i) [- both loss terms if with_loss] for every member; the caller sums Q over the ranks."""
+        sh = self._require_pairs(Q, g, f, n_batch, share)
+        self._check(self._lib.bfsm_collide_symmetric_batch_partial_async(self._h, _ptr(Q), _ptr(g), _ptr(f), int(n_batch), sh,
+                                                                         1 if with_loss else 0, ctypes.c_void_p(stream)))
+
+    def collideBilinearBatchPartial(self, Q, g, f, n_batch, with_loss, share=None, stream=0):
+        """This shard's part of Q(g_i, f_i) [- the loss term if with_loss] for every member; faithful handles only."""
+        sh = self._require_pairs(Q, g, f, n_batch, share)
+        self._check(self._lib.bfsm_collide_bilinear_batch_partial_async(self._h, _ptr(Q), _ptr(g), _ptr(f), int(n_batch), sh,
+                                                                        1 if with_loss else 0, ctypes.c_void_p(stream)))
+
     def computeCollisionSplit(self, Qgain, nu, f_in):
         """Blocking Qgain = Q+(f,f), nu = nu[f], device tensors; needs a handle that owns all directions."""
         self._require_batch(1, Qgain, nu, f_in)

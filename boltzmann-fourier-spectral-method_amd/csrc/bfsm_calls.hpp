@@ -50,6 +50,30 @@ void collide_symmetric(Pipe& p, double* Q, const double* g, const double* f, boo
     p.collide_symmetric(Q, g, f, with_loss);
 }
 
+// Member i of Q = Qs(g_i, f_i) (symmetric) or Q(g_i, f_i) of the shard [- the loss terms] for n_batch pairs
+// (bfsm_collide_symmetric_batch*_async, bfsm_collide_bilinear_batch_partial_async).  share (BFSM_SHARE_*): g or f is one array that
+// every member reads.  Fused cubes (Pipeline::collide_pairs): ONE sequence for the batch -- two spectra passes (a shared operand
+// transformed once: n_batch + 1 input transforms), per chunk the gain passes with the batch in the grid, one KC, one reduce (or
+// the reduce fused into the tail), one tail; with n_batch = 1 the launches of the single call.  Size-generic boxes: member by
+// member through collide_symmetric / collide_bilinear (a shared operand is transformed per member there).
+template <class Pipe>
+void collide_pairs(Pipe& p, double* Q, const double* g, const double* f, int n_batch, int share, bool with_loss, bool symmetric) {
+    if constexpr (Pipe::pair_batches) p.collide_pairs(Q, g, f, n_batch, share, with_loss, symmetric);
+    else {
+        const size_t G = p.plan.G();
+        for (int i = 0; i < n_batch; ++i) {
+            const double* gi = g + (share == BFSM_SHARE_G ? 0 : (size_t)i * G);
+            const double* fi = f + (share == BFSM_SHARE_F ? 0 : (size_t)i * G);
+            if (symmetric) p.collide_symmetric(Q + (size_t)i * G, gi, fi, with_loss);
+            else p.collide_bilinear(Q + (size_t)i * G, gi, fi, with_loss);
+        }
+    }
+}
+
+// Bytes the batched symmetric call moves on the fused pipeline (model): n_batch single calls, less the transform of a shared
+// operand (3.5 arrays) for every member but one
+inline double symmetric_batch_moved_bytes_per_eval(const PlanInfo& p, int n_batch, int share);
+
 // Bytes the symmetric call moves on the fused pipeline (model; the counterpart of moved_bytes_per_eval): per effective direction
 // four stored A' arrays written once and read once (two passes of A1', A2'; h = the stored share of the planes, (N/2 + 1)/N on
 // Hermitian handles), twice the segment sums and slabs, two transforms of an input and a three-plane tail (9 + 6.5 arrays).
@@ -61,6 +85,12 @@ inline double symmetric_moved_bytes_per_eval(const PlanInfo& p) {
     const double h = p.hermitian ? (double)(p.N / 2 + 1) / p.N : 1.0;
     const bool sums = p.exact_reductions || (p.precision == BFSM_F64 ? kb_sums_segments_n<double>(p.N) : kb_sums_segments_n<float>(p.N));
     return ((sums ? 8.0 * n * h + 8.0 * sg : 12.0 * n + 4.0 * sg) + 15.5) * G * c;
+}
+
+inline double symmetric_batch_moved_bytes_per_eval(const PlanInfo& p, int n_batch, int share) {
+    const double c = p.precision == BFSM_F64 ? 16.0 : 8.0;
+    const double saved = (p.N != 0 && share != BFSM_SHARE_NONE) ? 3.5 * (double)(n_batch - 1) * (double)p.G() * c : 0.0;
+    return (double)n_batch * symmetric_moved_bytes_per_eval(p) - saved;
 }
 
 // nu alone (bfsm_loss_rate_async)

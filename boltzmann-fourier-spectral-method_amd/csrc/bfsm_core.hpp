@@ -717,6 +717,56 @@ struct TailLineSymParams : TailLineParams<T> {
 template <class P> struct tail_line_sym { static constexpr bool value = false; };
 template <typename T> struct tail_line_sym<TailLineSymParams<T>> { static constexpr bool value = true; };
 
+// Batched two-operand forms (include/bfsm.h, bfsm_collide_symmetric_batch*, bfsm_collide_bilinear_batch*): every kernel that
+// reads an operand takes a member stride for each of the two, in elements: G = one array per member (blockIdx.z, blockIdx.y in
+// the tail line), 0 = one array that every member reads (BFSM_SHARE_G / BFSM_SHARE_F).  f_bstride belongs to the operand the base
+// type calls fhat / f, f2_bstride to fhat2 / f2.  Parameter types of their own again: the single-pair forms and every Q(f,f)
+// instantiation are the code they were.
+template <typename T>
+struct GainInvBiBatchParams : GainInvBiParams<T> {
+    size_t f_bstride, f2_bstride;
+};
+template <typename T> struct ka_bilinear<GainInvBiBatchParams<T>> { static constexpr bool value = true; };
+template <typename T>
+struct GainInvNyqBiBatchParams {
+    GainInvBiBatchParams<T> ka;
+    cx<T>* r;
+    size_t r_bstride;
+    int kn_blocks;
+    int ka_groups;
+};
+template <typename T>
+struct NyqRowsBiBatchParams : NyqRowsBiParams<T> {
+    size_t f_bstride, f2_bstride;
+};
+template <typename T> struct kn_bilinear<NyqRowsBiBatchParams<T>> { static constexpr bool value = true; };
+template <typename T>
+struct TailInvSymBatchParams : TailInvSymParams<T> {
+    size_t f_bstride, f2_bstride;      // of the loss spectra fhat and fhat + fhat2_off
+};
+template <typename T> struct tail_inv_sym<TailInvSymBatchParams<T>> { static constexpr bool value = true; };
+template <typename T>
+struct TailLineSymBatchParams : TailLineSymParams<T> {
+    size_t f_bstride, f2_bstride;      // of the real arrays f and f2
+};
+template <typename T> struct tail_line_sym<TailLineSymBatchParams<T>> { static constexpr bool value = true; };
+// the tail of the batched Q(g_i,f_i): the loss spectrum (f_hat) and the array that multiplies the loss (g) with a stride each
+template <typename T>
+struct TailInvBatchParams : TailInvParams<T> {
+    size_t f_bstride;
+};
+template <typename T>
+struct TailLineBatchParams : TailLineParams<T> {
+    size_t f_bstride;
+};
+template <class P> struct operand_strided { static constexpr bool value = false; };
+template <typename T> struct operand_strided<GainInvBiBatchParams<T>> { static constexpr bool value = true; };
+template <typename T> struct operand_strided<NyqRowsBiBatchParams<T>> { static constexpr bool value = true; };
+template <typename T> struct operand_strided<TailInvSymBatchParams<T>> { static constexpr bool value = true; };
+template <typename T> struct operand_strided<TailLineSymBatchParams<T>> { static constexpr bool value = true; };
+template <typename T> struct operand_strided<TailInvBatchParams<T>> { static constexpr bool value = true; };
+template <typename T> struct operand_strided<TailLineBatchParams<T>> { static constexpr bool value = true; };
+
 BFSM_HD int mode_of(int i, int n) { return i < n / 2 ? i : i - n; }
 
 // XCD-aware block index.  Workgroups are handed to the 8 XCDs round-robin by their linear id, and every XCD has its own
@@ -929,6 +979,10 @@ BFSM_HD void body_gain_inv(const P& prm, Ctx& ctx) {
     const cx<T>* src = prm.fhat + bz * N * N * N + (size_t)lxi * N * N;
     const cx<T>* src2 = src;                     // the conj(alpha) tile's plane
     if constexpr (BILIN) src2 = prm.fhat2 + bz * N * N * N + (size_t)lxi * N * N;
+    if constexpr (operand_strided<P>::value) {   // batched form: a member stride per spectrum (0: shared by every member)
+        src = prm.fhat + bz * prm.f_bstride + (size_t)lxi * N * N;
+        src2 = prm.fhat2 + bz * prm.f2_bstride + (size_t)lxi * N * N;
+    }
     if constexpr (KEEP) {
 #pragma unroll
         for (int m = 0; m < E; ++m) fh[m] = src[(u + TT * m) * N + p];  // [lz = u + T m][ly = p]
@@ -1360,6 +1414,7 @@ BFSM_HD void body_gain_inv_pair(const P& prm, Ctx& ctx) {
     const cx<T>* fsrc = prm.fhat;
     if constexpr (BILIN) { if (h) fsrc = prm.fhat2; }
     const cx<T>* src = fsrc + bz * N * N * N + (size_t)lxi * N * N;
+    if constexpr (operand_strided<P>::value) src = fsrc + bz * (h ? prm.f2_bstride : prm.f_bstride) + (size_t)lxi * N * N;
     cx<T> fh[E];
 #pragma unroll
     for (int m = 0; m < E; ++m) fh[m] = src[(u + TT * m) * N + p];  // [lz = u + T m][ly = p], both halves the same plane
@@ -1643,6 +1698,7 @@ BFSM_HD void body_nyq_rows(const P& prm, Ctx& ctx) {
     const cx<T>* spec = prm.fhat;
     if constexpr (kn_bilinear<P>::value) { if (conj) spec = prm.fhat2; }
     const cx<T>* fh = spec + (size_t)ctx.bz() * N * N * N + (size_t)idx * N * N;
+    if constexpr (operand_strided<P>::value) fh = spec + (size_t)ctx.bz() * (conj ? prm.f2_bstride : prm.f_bstride) + (size_t)idx * N * N;
     cx<T> v[E];
 #pragma unroll
     for (int m = 0; m < E; ++m) {
@@ -1711,6 +1767,23 @@ BFSM_HD void body_gain_inv_nyq(const GainInvNyqBiParams<T>& prm, Ctx& ctx) {
         NyqRowsBiParams<T> pk{};
         static_cast<NyqRowsParams<T>&>(pk) = NyqRowsParams<T>{prm.ka.fhat, prm.r, prm.ka.phx, prm.ka.phy, prm.ka.phz, prm.ka.tw, prm.ka.dir0, prm.r_bstride};
         pk.fhat2 = prm.ka.fhat2;
+        GuestCtx<Ctx> g(ctx, 0, kn);
+        body_nyq_rows<N, T>(pk, g);
+        return;
+    }
+    body_gain_inv<N, T>(prm.ka, ctx);
+}
+// the same for its batched form: both kernels with a member stride per spectrum
+template <int N, typename T, class Ctx>
+BFSM_HD void body_gain_inv_nyq(const GainInvNyqBiBatchParams<T>& prm, Ctx& ctx) {
+    if (ctx.by() >= prm.ka_groups) {                                     // workgroup-uniform
+        const int kn = (ctx.by() - prm.ka_groups) * ctx.gx() + ctx.bx();
+        if (kn >= prm.kn_blocks) return;
+        NyqRowsBiBatchParams<T> pk{};
+        static_cast<NyqRowsParams<T>&>(pk) = NyqRowsParams<T>{prm.ka.fhat, prm.r, prm.ka.phx, prm.ka.phy, prm.ka.phz, prm.ka.tw, prm.ka.dir0, prm.r_bstride};
+        pk.fhat2 = prm.ka.fhat2;
+        pk.f_bstride = prm.ka.f_bstride;
+        pk.f2_bstride = prm.ka.f2_bstride;
         GuestCtx<Ctx> g(ctx, 0, kn);
         body_nyq_rows<N, T>(pk, g);
         return;
@@ -2055,7 +2128,11 @@ BFSM_HD void body_tail_inv(const P& prm, Ctx& ctx) {
             const int mz = mode_of(u + TT * m, N);
             const T b2 = prm.beta2[mx * mx + my * my + mz * mz];
             cx<T> t;                                // symmetric form: plane y == 2 reads the second loss spectrum
-            if constexpr (tail_inv_sym<P>::value) t = prm.fhat[(long long)(ctx.by() >> 1) * prm.fhat2_off + (long long)(pbase + (u + TT * m) * N + p)];
+            if constexpr (tail_inv_sym<P>::value && operand_strided<P>::value) {      // batched: each loss spectrum with its member stride
+                const size_t ms = (ctx.by() >> 1) ? prm.f2_bstride : prm.f_bstride;
+                t = prm.fhat[(long long)(ctx.by() >> 1) * prm.fhat2_off + (long long)((size_t)ctx.bz() * ms + (size_t)lxi * N * N + (u + TT * m) * N + p)];
+            } else if constexpr (operand_strided<P>::value) t = prm.fhat[(size_t)ctx.bz() * prm.f_bstride + (size_t)lxi * N * N + (u + TT * m) * N + p];
+            else if constexpr (tail_inv_sym<P>::value) t = prm.fhat[(long long)(ctx.by() >> 1) * prm.fhat2_off + (long long)(pbase + (u + TT * m) * N + p)];
             else t = prm.fhat[pbase + (u + TT * m) * N + p];
             v[m] = {b2 * t.x, b2 * t.y};
         }
@@ -2080,6 +2157,10 @@ BFSM_HD void body_tail_line(const P& prm, Ctx& ctx) {
     int p, u;                                   // p: column inside this block of NPL
     lane_coords<NPL, Wg<N>::LROW>(ctx, p, u);
     const size_t base = (size_t)ctx.by() * N * N * N + (size_t)ctx.bx() * NPL + p;
+    // batched two-operand forms: the real operands with a member stride each (0: shared by every member)
+    size_t fbase = base, f2base = base;
+    if constexpr (operand_strided<P>::value) fbase = (size_t)ctx.by() * prm.f_bstride + (size_t)ctx.bx() * NPL + p;
+    if constexpr (operand_strided<P>::value && tail_line_sym<P>::value) f2base = (size_t)ctx.by() * prm.f2_bstride + (size_t)ctx.bx() * NPL + p;
     cx<T>* lds = ctx.template lds<cx<T>>();
     Twiddles<N, T> twr;
     twr.load(prm.tw, u, ctx);
@@ -2094,14 +2175,14 @@ BFSM_HD void body_tail_line(const P& prm, Ctx& ctx) {
             for (int m = 0; m < E; ++m) l[m] = prm.tl[base + (size_t)(u + TT * m) * N * N];
             fft_line_np<N, NPL, +1, T>(l, lds, p, u, twr, ctx);
 #pragma unroll
-            for (int m = 0; m < E; ++m) q[m] = (double)g[m].x - (double)l[m].x * prm.f[base + (size_t)(u + TT * m) * N * N];
+            for (int m = 0; m < E; ++m) q[m] = (double)g[m].x - (double)l[m].x * prm.f[fbase + (size_t)(u + TT * m) * N * N];
 #pragma unroll
             for (int m = 0; m < E; ++m) l[m] = prm.tl2[base + (size_t)(u + TT * m) * N * N];
             fft_line_np<N, NPL, +1, T>(l, lds, p, u, twr, ctx);
 #pragma unroll
             for (int m = 0; m < E; ++m) {
                 const size_t i = base + (size_t)(u + TT * m) * N * N;
-                prm.Q[i] = q[m] - (double)l[m].x * prm.f2[i];
+                prm.Q[i] = q[m] - (double)l[m].x * prm.f2[f2base + (size_t)(u + TT * m) * N * N];
             }
         } else {
 #pragma unroll
@@ -2124,7 +2205,7 @@ BFSM_HD void body_tail_line(const P& prm, Ctx& ctx) {
 #pragma unroll
         for (int m = 0; m < E; ++m) {
             const size_t i = base + (size_t)(u + TT * m) * N * N;
-            prm.Q[i] = (double)g[m].x - (double)l[m].x * prm.f[i];
+            prm.Q[i] = (double)g[m].x - (double)l[m].x * prm.f[fbase + (size_t)(u + TT * m) * N * N];
         }
     } else {
 #pragma unroll

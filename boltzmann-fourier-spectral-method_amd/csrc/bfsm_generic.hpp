@@ -1297,6 +1297,10 @@ struct GenericPipeline : DeviceBuffers<Backend> {
 
     // Bilinear form Q(g,f): as Pipeline::collide_bilinear (g_hat in fhat, f_hat in fhat + G: init reserves two spectra)
     cx<T>* fhat_b() const { return fhat + G; }
+    // the batched two-operand forms (bfsm_calls.hpp, collide_pairs) run member by member through the two functions below on this
+    // path: a shared operand is transformed again for every member
+    static constexpr bool pair_batches = false;
+    void collide_pairs(double*, const double*, const double*, int, int, bool, bool) {}
     void collide_bilinear(double* Q_dev, const double* g_dev, const double* f_dev, bool with_loss, double* nu_dev = nullptr) {
         spectrum(g_dev, fhat, 1);
         const cx<T>* fb = fhat;

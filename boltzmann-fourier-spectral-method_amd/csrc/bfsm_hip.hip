@@ -863,6 +863,55 @@ int bfsm_collide_symmetric(bfsm_handle h, double* Q_dev, const double* g_dev, co
     return bfsm_synchronize(h);
 }
 
+// Batched two-operand forms: n_batch pairs through one sequence (bfsm_calls.hpp, collide_pairs), a shared operand read by every
+// member.  All argument checks come before the first launch: an error writes nothing.
+static int collide_pairs_entry(bfsm_plan* h, double* Q_dev, const double* g_dev, const double* f_dev, int n_batch, int share,
+                               int with_loss, void* stream, bool symmetric, const char* where) {
+    if (!h) return BFSM_ERR_INVALID;
+    BFSM_GUARDED(h,
+        DeviceGuard guard(h->desc.device);
+        int rc = enter(h, guard, stream);
+        if (rc) return rc;
+        if (!g_dev || !f_dev || !Q_dev) return fail(h, BFSM_ERR_INVALID, "null Q, g or f");
+        if (share != BFSM_SHARE_NONE && share != BFSM_SHARE_G && share != BFSM_SHARE_F)
+            return fail(h, BFSM_ERR_INVALID, "share must be BFSM_SHARE_NONE, BFSM_SHARE_G or BFSM_SHARE_F");
+        int cap = 1;
+        h->with([&](auto& p) { cap = p.max_batch; });
+        if (n_batch < 1 || n_batch > cap)
+            return fail(h, BFSM_ERR_INVALID, "n_batch must be in [1, max_batch of the descriptor]");
+        if (!symmetric && (h->desc.flags & BFSM_FLAG_EXACT_REDUCTIONS))
+            return fail(h, BFSM_ERR_UNSUPPORTED, "the bilinear form needs a handle without BFSM_FLAG_EXACT_REDUCTIONS (its antipodal merge assumes g = f)");
+        const size_t nq = (size_t)n_batch * h->G;
+        auto overlaps = [&](const double* a, size_t na) { return a < Q_dev + nq && Q_dev < a + na; };
+        if (overlaps(g_dev, share == BFSM_SHARE_G ? h->G : nq) || overlaps(f_dev, share == BFSM_SHARE_F ? h->G : nq))
+            return fail(h, BFSM_ERR_INVALID, "Q must not overlap g or f");
+        if (conserving(h) && (rc = check_cons_q(h, Q_dev))) return rc;
+        h->be.begin_eval();
+        h->with([&](auto& p) { bfsm::collide_pairs(p, Q_dev, g_dev, f_dev, n_batch, share, with_loss != 0, symmetric); });
+        if (conserving(h)) h->cons->apply(Q_dev, n_batch);
+        return leave(h, where);
+    )
+}
+
+int bfsm_collide_symmetric_batch_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, int n_batch,
+                                               int share, int with_loss, void* stream) {
+    return collide_pairs_entry(h, Q_dev, g_dev, f_dev, n_batch, share, with_loss, stream, true, "bfsm_collide_symmetric_batch");
+}
+
+int bfsm_collide_bilinear_batch_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, int n_batch,
+                                              int share, int with_loss, void* stream) {
+    return collide_pairs_entry(h, Q_dev, g_dev, f_dev, n_batch, share, with_loss, stream, false, "bfsm_collide_bilinear_batch");
+}
+
+int bfsm_collide_symmetric_batch(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, int n_batch, int share) {
+    if (!h) return BFSM_ERR_INVALID;
+    if (!h->full_shard)
+        return fail(h, BFSM_ERR_INVALID, "bfsm_collide_symmetric_batch needs a handle that owns all directions; use bfsm_collide_symmetric_batch_partial_async + a sum over the ranks");
+    int rc = bfsm_collide_symmetric_batch_partial_async(h, Q_dev, g_dev, f_dev, n_batch, share, 1, nullptr);
+    if (rc) return rc;
+    return bfsm_synchronize(h);
+}
+
 // Gain / loss split: the sequences of bfsm_collide_batch_partial_async / bfsm_collide_bilinear_partial_async with the two terms
 // of the tail kept apart (Pipeline::finish / GenericPipeline::finish with nu_dev).  N = 16 takes the plane-tile pipeline.  No
 // projection: BFSM_FLAG_CONSERVE applies to Q, not to its parts.

@@ -361,11 +361,17 @@ constexpr size_t small_kernel_lds_bytes() { return kind == SK::Reduce ? 256 * si
     else if constexpr (kind == SK::Reduce) body_small_reduce<T>(prm, ctx);
 
 // fn(std::integral_constant<int, N>{}) for the cube size N of the fused pipeline (fused_grid); false: not one of them
+// BFSM_FUSED_N_MAX (test harness builds only, e.g. a sanitizer build of the host emulator): larger cubes are not instantiated
+#ifndef BFSM_FUSED_N_MAX
+#define BFSM_FUSED_N_MAX 128
+#endif
 template <class F>
 bool for_fused_n(int N, F&& fn) {
+    if (N > BFSM_FUSED_N_MAX) return false;
     switch (N) {
         case 16: fn(std::integral_constant<int, 16>{}); return true;
         case 24: fn(std::integral_constant<int, 24>{}); return true;
+#if BFSM_FUSED_N_MAX >= 128
         case 32: fn(std::integral_constant<int, 32>{}); return true;
         case 40: fn(std::integral_constant<int, 40>{}); return true;
         case 48: fn(std::integral_constant<int, 48>{}); return true;
@@ -373,6 +379,7 @@ bool for_fused_n(int N, F&& fn) {
         case 64: fn(std::integral_constant<int, 64>{}); return true;     // code object, which follows the instantiations here)
         case 96: fn(std::integral_constant<int, 96>{}); return true;
         case 128: fn(std::integral_constant<int, 128>{}); return true;
+#endif
         default: return false;
     }
 }
@@ -428,7 +435,7 @@ struct Pipeline : DeviceBuffers<Backend> {
     cx<T>* pseg = nullptr;        // [segment][x][y][z]
     Segment* segs_unit = nullptr; // one single-slot segment per pseg entry, same r
     T* ones = nullptr;
-    cx<T>* slab_sym = nullptr;    // symmetric form: [2 slab_count] slabs and segment sums, the second loss array of its tail
+    cx<T>* slab_sym = nullptr;    // symmetric form: [max_batch][2 slab_count] slabs and segment sums, [max_batch] second loss arrays
     cx<T>* pseg_sym = nullptr;
     cx<T>* tl_sym = nullptr;
     cx<T>* rnyq = nullptr;        // Hermitian mode: Nyquist rows [slot][sign][kind][N/2-1][N]
@@ -459,8 +466,9 @@ struct Pipeline : DeviceBuffers<Backend> {
         slab_count = plan.segs.size();
         const size_t nslab = slab_count ? slab_count : 1;
         bool ok = true;
-        // at least two spectra: the bilinear form Q(g,f) keeps g_hat and f_hat (collide_bilinear)
-        ok = ok && dev_alloc(fhat, (nb > 2 ? nb : 2) * G);
+        // two spectra per member: the bilinear and symmetric forms keep g_hat [max_batch][G] and f_hat [max_batch][G]
+        // (collide_bilinear, collide_pairs); two in all on a max_batch <= 1 handle, as ever
+        ok = ok && dev_alloc(fhat, 2 * nb * G);
         ok = ok && dev_alloc(tg, 2 * nb * G);
         if (ok) tl = tg + nb * G;
         ok = ok && dev_alloc(qhat, nb * G);
@@ -500,10 +508,11 @@ struct Pipeline : DeviceBuffers<Backend> {
             ok = ok && dev_alloc(small_part, (size_t)(small_wgs + 1) * G);
         }
         // Scratch of the symmetric form alone, allocated last so that every buffer of the other entry points is made in the order
-        // and size it always was: 2 x slab_count slabs and segment sums of one distribution, and the second loss array
-        ok = ok && dev_alloc(slab_sym, 2 * nslab * G);
-        if (segment_sums()) ok = ok && dev_alloc(pseg_sym, 2 * nslab * G);
-        ok = ok && dev_alloc(tl_sym, G);
+        // and size it always was: per member 2 x slab_count slabs and segment sums (member stride 2 x slab_count x G) and the
+        // second loss array; on a max_batch <= 1 handle the sizes they always had
+        ok = ok && dev_alloc(slab_sym, nb * 2 * nslab * G);
+        if (segment_sums()) ok = ok && dev_alloc(pseg_sym, nb * 2 * nslab * G);
+        ok = ok && dev_alloc(tl_sym, nb * G);
         if (!ok) { err = "device allocation failed"; return BFSM_ERR_NOMEM; }
         return BFSM_OK;
     }
@@ -609,24 +618,93 @@ struct Pipeline : DeviceBuffers<Backend> {
         be->template launch<K::TailLine, T>(line_blocks(), 1, 1, tb, N);
     }
 
+    // Batched two-operand forms (include/bfsm.h, bfsm_collide_symmetric_batch*, bfsm_collide_bilinear_batch*): member i of Q is
+    // Qs(g_i, f_i) (symmetric) or Q(g_i, f_i) for nb <= max_batch members, every launch covering the batch.  share
+    // (BFSM_SHARE_G / BFSM_SHARE_F): that operand is ONE array all members read -- transformed once into one spectrum, read by
+    // the kernels with a member stride of 0.  g_hat at fhat [max_batch][G], f_hat behind it; with nb = 1 the launches of
+    // collide_symmetric / collide_bilinear, and every member is bitwise what they give on that member's operands.
+    static constexpr bool pair_batches = true;        // one sequence for the whole batch (GenericPipeline: member by member)
+    void collide_pairs(double* Q_dev, const double* g_dev, const double* f_dev, int nb, int share, bool with_loss, bool symmetric) {
+        const int N = plan.N;
+        const size_t G = plan.G();
+        const size_t g_bs = share == BFSM_SHARE_G ? 0 : G, f_bs = share == BFSM_SHARE_F ? 0 : G;
+        cx<T>* const ghat = fhat;
+        cx<T>* const fhat_f = fhat + (size_t)max_batch * G;
+        spectrum(g_dev, ghat, g_bs ? nb : 1);
+        const cx<T>* fb = ghat;                                   // g == f: one transform per member, both operands read it
+        if (!(f_dev == g_dev && share == BFSM_SHARE_NONE)) { spectrum(f_dev, fhat_f, f_bs ? nb : 1); fb = fhat_f; }
+        const OperandSpectra sp{ghat, fb, g_bs, f_bs};
+        const double Gc = (double)G * cbytes() * nb;
+        const size_t nslab = slab_count ? slab_count : 1;
+        if (symmetric) {
+            const bool fu = fuse_reduce_symmetric();
+            gain_spectra(nb, !fu, nullptr, true, &sp);
+            const size_t n_slabs = 2 * slab_count;
+            TailInvSymBatchParams<T> ta{};
+            static_cast<TailInvParams<T>&>(ta) = TailInvParams<T>{qhat, fb, beta2, tg, (long long)(tl - tg), tw, slab_sym, beta1, segs,
+                                                                   fu ? (int)n_slabs : -1, plan.n2stride, 2 * nslab * G};
+            ta.fhat2_off = (long long)(ghat - fb);
+            ta.tl2_off = (long long)(tl_sym - tg);
+            ta.f_bstride = f_bs;
+            ta.f2_bstride = g_bs;
+            be->mark(BFSM_K_TAIL, ((with_loss ? 6.0 : 2.0) + (fu ? (double)n_slabs - 1.0 : 0.0)) * Gc);
+            be->template launch<K::TailInv, T>(N, with_loss ? 3 : 1, nb, ta, N);
+            TailLineSymBatchParams<T> tb{};
+            static_cast<TailLineParams<T>&>(tb) = TailLineParams<T>{tg, tl, g_dev, Q_dev, tw, with_loss ? 1 : 0};
+            tb.tl2 = tl_sym;
+            tb.f2 = f_dev;
+            tb.f_bstride = g_bs;
+            tb.f2_bstride = f_bs;
+            be->mark(BFSM_K_TAIL, (with_loss ? 5.0 : 1.5) * Gc);
+            be->template launch<K::TailLine, T>(line_blocks(), nb, 1, tb, N);
+        } else {
+            const bool fu = fuse_reduce();
+            gain_spectra(nb, !fu, nullptr, false, &sp);
+            TailInvBatchParams<T> ta{};
+            static_cast<TailInvParams<T>&>(ta) = TailInvParams<T>{qhat, fb, beta2, tg, (long long)(tl - tg), tw, slab, beta1, segs,
+                                                                   fu ? (int)slab_count : -1, plan.n2stride, nslab * G};
+            ta.f_bstride = f_bs;
+            be->mark(BFSM_K_TAIL, ((with_loss ? 4.0 : 2.0) + (fu ? (double)slab_count - 1.0 : 0.0)) * Gc);
+            be->template launch<K::TailInv, T>(N, with_loss ? 2 : 1, nb, ta, N);
+            TailLineBatchParams<T> tb{};
+            static_cast<TailLineParams<T>&>(tb) = TailLineParams<T>{tg, tl, g_dev, Q_dev, tw, with_loss ? 1 : 0};
+            tb.f_bstride = g_bs;
+            be->mark(BFSM_K_TAIL, (with_loss ? 3.0 : 1.5) * Gc);
+            be->template launch<K::TailLine, T>(line_blocks(), nb, 1, tb, N);
+        }
+    }
+
     // The gain term of this shard from the spectra in fhat (and fhat2 for the bilinear form: the conj(alpha) operand) into qhat.
     // symmetric (one distribution, fhat2 given): every chunk runs a second pass with the two spectra exchanged, whose segment
     // sums and slabs are the entries slab_count + i of slab_sym / pseg_sym; KC, the reduce and the fused tail then cover 2 x slab_count entries, so
     // qhat = gain_hat[g,f] + gain_hat[f,g] in one fixed order.
-    void gain_spectra(int nb, bool do_reduce, const cx<T>* fhat2, bool symmetric = false) {
+    // pairs (the batched two-operand forms, collide_pairs): the spectra of the nb members' operands, each with its member stride
+    // (0: one spectrum that every member reads); the kernels that read a spectrum then take their batched parameter types, and
+    // fhat2 is not read.  The member stride of the symmetric form's slabs and segment sums is 2 x slab_count x G.
+    struct OperandSpectra {
+        const cx<T>* a;       // the alpha operand (g_hat)
+        const cx<T>* b;       // the conj(alpha) operand (f_hat)
+        size_t a_bstride, b_bstride;
+    };
+    void gain_spectra(int nb, bool do_reduce, const cx<T>* fhat2, bool symmetric = false, const OperandSpectra* pairs = nullptr) {
         const int N = plan.N;
         const double Gc = (double)plan.G() * cbytes() * nb;
         const size_t G = plan.G();
-        const size_t a_bs = cap * (size_t)a_planes * N * N, s_bs = (slab_count ? slab_count : 1) * G;
+        const int n_pass = symmetric ? 2 : 1;
+        const size_t a_bs = cap * (size_t)a_planes * N * N, s_bs = (size_t)n_pass * (slab_count ? slab_count : 1) * G;
         const size_t r_bs = cap * r_per_dir();
         const double hfrac = (double)a_planes / N;                 // share of A' actually stored
-        const int n_pass = symmetric ? 2 : 1;
         cx<T>* const slab = symmetric ? slab_sym : this->slab;       // the symmetric form's own slabs and segment sums
         cx<T>* const pseg = symmetric ? pseg_sym : this->pseg;
         const size_t n_slabs = slab_count * (size_t)n_pass;
         for (const Chunk& c : plan.chunks) for (int pass = 0; pass < n_pass; ++pass) {
             const cx<T>* fa = pass ? fhat2 : fhat;               // the alpha operand's spectrum
             const cx<T>* fb = pass ? fhat : fhat2;               // the conj(alpha) operand's (null: Q(f,f))
+            size_t fa_bs = G, fb_bs = G;
+            if (pairs) {
+                fa = pass ? pairs->b : pairs->a; fa_bs = pass ? pairs->b_bstride : pairs->a_bstride;
+                fb = pass ? pairs->a : pairs->b; fb_bs = pass ? pairs->a_bstride : pairs->b_bstride;
+            }
             const int seg0 = c.seg0 + pass * (int)slab_count;
             // KA's parallelism is planes x direction groups: keep >= 2 workgroups per CU when only N/2 + 1 planes run
             const int tw_ = target_workgroups(N, max_batch);
@@ -649,7 +727,18 @@ struct Pipeline : DeviceBuffers<Backend> {
             const int kn_blocks = kn_rides ? 2 * c.n : 0, kn_rows = (kn_blocks + a_planes - 1) / a_planes;
             GainInvParams<T> ka{fa, a1, a2, phx, phy, phz, tw, c.dir0, c.n, per_group_a, a_bs, a_planes, warm ? 1 : 0};
             be->mark(BFSM_K_GAIN_INV, 2.0 * c.n * Gc * hfrac);
-            if (fb) {                           // two operands: Q(g,f) on faithful handles, Qs(g,f) on every mode
+            if (pairs) {                        // batched two-operand forms: a member stride per spectrum
+                GainInvBiBatchParams<T> kab{};
+                static_cast<GainInvParams<T>&>(kab) = ka;
+                kab.fhat2 = fb;
+                kab.f_bstride = fa_bs;
+                kab.f2_bstride = fb_bs;
+                if (kn_rides) {
+                    GainInvNyqBiBatchParams<T> kan{kab, rnyq, r_bs, kn_blocks, ga};
+                    be->template launch<K::GainInvNyq, T>(a_planes, ga + kn_rows, nb, kan, N);
+                } else if (pair_geometry() && !interleaved()) be->template launch<K::GainInvTwo, T>(a_planes, ga, nb, kab, N);
+                else be->template launch<K::GainInv, T>(a_planes, ga, nb, kab, N);
+            } else if (fb) {                    // two operands: Q(g,f) on faithful handles, Qs(g,f) on every mode
                 GainInvBiParams<T> kab{};
                 static_cast<GainInvParams<T>&>(kab) = ka;
                 kab.fhat2 = fb;
@@ -685,7 +774,14 @@ struct Pipeline : DeviceBuffers<Backend> {
                     NyqRowsParams<T> kn{fa, rnyq, phx, phy, phz, tw, c.dir0, r_bs};
                     const int npl = line_npl(N), ncol = 2 * (N / 2 - 1);
                     be->mark(BFSM_K_GAIN_INV, 0.0);
-                    if (fb) {
+                    if (pairs) {
+                        NyqRowsBiBatchParams<T> knb{};
+                        static_cast<NyqRowsParams<T>&>(knb) = kn;
+                        knb.fhat2 = fb;
+                        knb.f_bstride = fa_bs;
+                        knb.f2_bstride = fb_bs;
+                        be->template launch<K::NyqRows, T>((ncol + npl - 1) / npl, 2 * c.n, nb, knb, N);
+                    } else if (fb) {
                         NyqRowsBiParams<T> knb{};
                         static_cast<NyqRowsParams<T>&>(knb) = kn;
                         knb.fhat2 = fb;

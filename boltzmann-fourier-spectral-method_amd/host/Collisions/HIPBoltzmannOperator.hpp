@@ -54,6 +54,13 @@ public:
     // Symmetric form Qs(g,f) = Q(g,f) + Q(f,g) (include/bfsm.h, bfsm_collide_symmetric): device pointers, blocking; served by
     // every handle, the exact and Hermitian modes included.  L_f[h] = Qs(f,h).
     void computeSymmetricCollision(double* Q, const double* g, const double* f);
+    // Batched two-operand forms (include/bfsm.h, bfsm_collide_symmetric_batch*, bfsm_collide_bilinear_batch_partial_async):
+    // Q[i] = Qs(g_i, f_i) / Q(g_i, f_i) for n_batch <= setMaxBatch() pairs in one launch sequence; share = BFSM_SHARE_NONE, or
+    // BFSM_SHARE_G / BFSM_SHARE_F: that operand is one array of G doubles every member uses.  The first is blocking; the two
+    // partial forms enqueue on `stream` (a hipStream_t) for this handle's direction shard, as the C calls do.
+    void computeSymmetricCollisionBatch(double* Q, const double* g, const double* f, int n_batch, int share = 0);
+    void collideSymmetricBatchPartial(double* Q, const double* g, const double* f, int n_batch, int share, bool with_loss, void* stream = nullptr);
+    void collideBilinearBatchPartial(double* Q, const double* g, const double* f, int n_batch, int share, bool with_loss, void* stream = nullptr);
 
     // Gain / loss split (include/bfsm.h, bfsm_collide_split): Qgain = Q+(f,f), nu = the collision frequency nu[f], so that
     // Q = Qgain - f * nu; device pointers, blocking.  lossRate: nu alone, without any gain work (blocking).

@@ -51,6 +51,20 @@ void BoltzmannOperator<HIP_Backend>::computeSymmetricCollision(double* Q, const 
     check(bfsm_collide_symmetric(handle_, Q, g, f), "computeSymmetricCollision");
 }
 
+void BoltzmannOperator<HIP_Backend>::computeSymmetricCollisionBatch(double* Q, const double* g, const double* f, int n_batch, int share) {
+    check(bfsm_collide_symmetric_batch(handle_, Q, g, f, n_batch, share), "computeSymmetricCollisionBatch");
+}
+
+void BoltzmannOperator<HIP_Backend>::collideSymmetricBatchPartial(double* Q, const double* g, const double* f, int n_batch, int share,
+                                                                  bool with_loss, void* stream) {
+    check(bfsm_collide_symmetric_batch_partial_async(handle_, Q, g, f, n_batch, share, with_loss ? 1 : 0, stream), "collideSymmetricBatchPartial");
+}
+
+void BoltzmannOperator<HIP_Backend>::collideBilinearBatchPartial(double* Q, const double* g, const double* f, int n_batch, int share,
+                                                                 bool with_loss, void* stream) {
+    check(bfsm_collide_bilinear_batch_partial_async(handle_, Q, g, f, n_batch, share, with_loss ? 1 : 0, stream), "collideBilinearBatchPartial");
+}
+
 void BoltzmannOperator<HIP_Backend>::computeCollisionSplit(double* Qgain, double* nu, const double* f_in) {
     check(bfsm_collide_split(handle_, Qgain, nu, f_in), "computeCollisionSplit");
 }

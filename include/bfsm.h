@@ -237,7 +237,8 @@ int bfsm_collide_bilinear_partial_async(bfsm_handle h, double* Q_dev, const doub
  *     gain(g,f) + gain(f,g) = sum_{s < M/2} 2 w_s [P_s(g,f) + P_s(f,g)]:
  * the merged plan (M/2 directions, doubled weights) applied to both operand orders.  Both operand orders are computed for
  * every direction on every handle, so rules without that symmetry are served as well (unmerged, every direction twice).
- *   - g, f, Q: device pointers to one distribution each; a handle created with max_batch > 1 serves a single call.  g == f
+ *   - g, f, Q: device pointers to one distribution each; a handle created with max_batch > 1 serves a single call (batches of
+ *     pairs: bfsm_collide_symmetric_batch* below).  g == f
  *     (the same pointer) is allowed; Q must not overlap g or f (BFSM_ERR_INVALID); a null pointer gives BFSM_ERR_INVALID.
  *   - routes.  Fused cubes, every mode and both precisions: per chunk two passes of the gain kernels with the spectra
  *     exchanged -- KA (the bilinear operand selection, in the Hermitian mode with planes = N/2 + 1, its two-array form at
@@ -264,6 +265,42 @@ int bfsm_collide_symmetric(bfsm_handle h, double* Q_dev, const double* g_dev, co
 int bfsm_collide_symmetric_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, void* stream);
 int bfsm_collide_symmetric_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev,
                                          int with_loss, void* stream);
+
+/*
+ * Batched two-operand forms (new functionality; the presence of these symbols is the capability check, BFSM_VERSION stays 2):
+ * member i of Q is Qs(g_i, f_i) (bfsm_collide_symmetric_batch*) or Q(g_i, f_i) (bfsm_collide_bilinear_batch_partial_async) for
+ * n_batch pairs in ONE launch sequence -- what a Newton-Krylov or linearized-implicit step of a spatially inhomogeneous problem
+ * applies in every cell, L_{f_i}[h_i] = Qs(f_i, h_i), and what a block Krylov method, Jacobian probing or a two-species cross
+ * term applies to many h_i with one shared f, Qs(f, h_i).
+ *   - Q is [n_batch][G], 1 <= n_batch <= max_batch of the descriptor.  An operand that is not shared is [n_batch][G].  With
+ *     share = BFSM_SHARE_G (BFSM_SHARE_F), g (f) is ONE array of G doubles used by every member: member i of Q is Qs(g, f_i)
+ *     (Qs(g_i, f)), likewise Q(.,.).  g == f as the same pointer with BFSM_SHARE_NONE is allowed and gives 2 Q(f_i, f_i).
+ *     Q must not overlap any array that is read.  A null pointer, a bad n_batch or a bad share: BFSM_ERR_INVALID, nothing written.
+ *   - the symmetric forms run on every handle (faithful, exact, Hermitian, both precisions, N = 16 on the plane-tile pipeline,
+ *     size-generic boxes, direction shards: exactly one rank passes with_loss != 0, as for the single call).  The bilinear form
+ *     returns BFSM_ERR_UNSUPPORTED on exact-reduction handles and leaves Q untouched, like bfsm_collide_bilinear*.
+ *   - member i is bitwise bfsm_collide_symmetric_partial_async / bfsm_collide_bilinear_partial_async on member i's operands ON THE
+ *     SAME HANDLE; it does not depend on n_batch, on share or on what the other members hold; repeated calls are bitwise
+ *     identical (fixed-order sums, no atomics).  BFSM_FLAG_CONSERVE projects every member (Q 16-byte aligned).
+ *   - fused cubes: two spectra passes, then per chunk the two gain passes with the batch in the grid, one forward-tile pass, one
+ *     reduce (fused into the tail when 2 x slabs <= 8), one three-plane tail; with n_batch = 1 the launches of the single call.  A
+ *     shared operand is transformed ONCE into one spectrum that every member's kernels read (member stride 0): n_batch + 1 input
+ *     transforms per call instead of 2 n_batch.  Every member still writes its own four A' arrays per direction.  Scratch scales
+ *     with max_batch (2 max_batch spectra, max_batch x the symmetric slabs and segment sums, max_batch second loss arrays);
+ *     with max_batch <= 1 every allocation of the handle is what it was.
+ *   - size-generic boxes: the batch runs member by member through the single calls; a shared operand is transformed again for
+ *     every member there.
+ *   - bfsm_collide_symmetric_batch is blocking and needs a handle that owns all directions; the _async forms are allocation-free
+ *     after bfsm_create, graph-capturable after one evaluation outside a capture and tracked by bfsm_synchronize.  With
+ *     BFSM_FLAG_PROFILE the counters cover the sequence; the byte model (symmetric_batch_moved_bytes_per_eval in
+ *     csrc/bfsm_calls.hpp) scales with n_batch except for the transform of a shared operand.
+ */
+enum { BFSM_SHARE_NONE = 0, BFSM_SHARE_G = 1, BFSM_SHARE_F = 2 };
+int bfsm_collide_symmetric_batch(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, int n_batch, int share);
+int bfsm_collide_symmetric_batch_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, int n_batch,
+                                               int share, int with_loss, void* stream);
+int bfsm_collide_bilinear_batch_partial_async(bfsm_handle h, double* Q_dev, const double* g_dev, const double* f_dev, int n_batch,
+                                              int share, int with_loss, void* stream);
 
 /*
  * Gain / loss split (new functionality; the presence of these symbols is the capability check, BFSM_VERSION stays 2).
